@@ -8,11 +8,21 @@ HBM.  With --gpus N each rank (one process per GPU, torch.distributed.run)
 evaluates its own 4096 keys: weak scaling, no collective on the data path;
 value = points of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line: the metric, a "roofline" object for the tree
-kernel (integer-VALU bound; its time from HIP events recorded on the launch
-stream around every k_evalfull of the timed steps), and a "cpu_baseline"
-object (the oracle's reference-faithful C restatement on AES-NI, timed on a
-bounded sample on this host).
+Rank 0 prints ONE JSON line: the metric and a "roofline" object for the tree
+kernel (its time from HIP events recorded on the launch stream around
+sampled k_evalfull launches of the timed steps).  A plain run does no more
+than that: set up, spin up, warm up, time the steps, print.
+
+--full adds everything that takes runs of its own: a "cpu_baseline" object
+(the oracle's reference-faithful C restatement on AES-NI, timed on a bounded
+sample on this host), the other AES back end ("aes_variants"), the
+host-buffer API rates ("api", "single_call", the reference's own timing
+shapes), the configs[2..4] sub-lines ("workloads") and the PIR batch sweep.
+The --no-* options switch single parts of a --full run off again.
+
+--dump-outputs DIR writes what the last timed step left in its output buffer
+as DIR/<name>.npy (see dump_u8): the inputs are seeded, so two builds can be
+compared output for output.
 
 Secondary workloads (--workload), each its own JSON line:
   eval   configs[2]: 2^16 keys x 2^10 random points, logN=20 per GPU (weak)
@@ -47,6 +57,11 @@ GUIDE_GATE_PEAK_T = GUIDE_VALU_TOPS * 32 * 2
 GUIDE_LDS_LOOKUPS_T = 75e12 / 4 / 1e12
 HBM_PEAK_GBS = 8000.0
 METRIC = "DPF leaf points/sec (EvalFull logN=20, batched keys) + AES blocks/sec"
+# --dump-outputs: 2^22 sampled bytes (16 MiB as float32) of a larger output, and
+# the width of a row of a flat buffer's row sums (Ctx.dump).
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 0x5EEDD9F2
+DUMP_ROW = 4096
 
 
 def stop_of(logN: int) -> int:
@@ -371,8 +386,43 @@ class Ctx:
         k_ms = (sum(evs[i][0].elapsed_time(evs[i][1]) for i in timed_i) / len(timed_i)) if timed_i else float("nan")
         return t_wall, k_ms
 
+    def dump(self, name, out):
+        """--dump-outputs: write the output buffer of the last timed step (a
+        uint8 torch tensor or numpy array, `out`) under DIR.  Up to
+        DUMP_SAMPLE bytes are written whole; of a larger buffer, the bytes at
+        DUMP_SAMPLE fixed positions (sorted draws of a generator seeded with
+        DUMP_SEED, the same for every run of one shape) as <name>.npy, and the
+        sum of each of its rows (each key's bytes) as <name>_rowsum.npy, so
+        every output byte enters some figure.  float32 / float64 hold these
+        integers exactly.  With several ranks each writes its own
+        <name>_rank<r>."""
+        d = self.args.dump_outputs
+        if not d:
+            return
+        torch = self.torch
+        os.makedirs(d, exist_ok=True)
+        if self.world > 1:
+            name = f"{name}_rank{self.rank}"
+        t = out if isinstance(out, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(out))
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+            sample = flat[torch.from_numpy(idx).to(flat.device)]
+            if t.dim() > 1:
+                sums = t.reshape(t.shape[0], -1).sum(dim=1, dtype=torch.int64)
+            else:                                  # a flat buffer: rows of DUMP_ROW bytes, then the tail
+                cut = n - n % DUMP_ROW
+                sums = torch.cat([flat[:cut].reshape(-1, DUMP_ROW).sum(dim=1, dtype=torch.int64),
+                                  flat[cut:].sum(dtype=torch.int64).reshape(1)])
+            np.save(os.path.join(d, f"{name}_rowsum.npy"), sums.cpu().numpy().astype(np.float64))
+        else:
+            sample = flat
+        np.save(os.path.join(d, f"{name}.npy"), sample.cpu().numpy().astype(np.float32))
+
     def line(self, **kw):
         base = {"n_gpus": self.world, "steps": self.args.steps, "warmup": self.args.warmup,
+                "full": bool(self.args.full),
                 "spinup_s": self.args.spinup, "event_every": self.args.event_every,
                 "higher_is_better": True, "vs_baseline": None, "dtype": "u32"}
         base.update(kw)
@@ -415,6 +465,7 @@ def wl_evalfull(c: Ctx) -> dict:
     names = {dpf.AES_TTABLE: "lds-ttable", dpf.AES_BITSLICED: "bitsliced"}
     main_impl = dpf.get_aes_impl()
     t_wall, k_ms = c.timed(step, a.steps, a.warmup)
+    c.dump("evalfull_out", d_out.view(nk, olen))
     sec = t_wall / a.steps
     aes = nk * aes_full(logN)
     variants = {names[main_impl]: {"ms_per_step": sec * 1e3, "kernel_ms": k_ms,
@@ -697,6 +748,7 @@ def wl_eval(c: Ctx) -> dict:
             ev[1].record(c.stream)
 
     t_wall, k_ms = c.timed(step, a.steps, a.warmup)
+    c.dump("eval_out", d_out.view(nk, ppk))
     if a.check and c.rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
@@ -752,6 +804,7 @@ def wl_split(c: Ctx) -> dict:
             ev[1].record(c.stream)
 
     t_wall, k_ms = c.timed(step, a.steps, a.warmup)
+    c.dump("split_out", d_out)
     if a.check and c.rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
@@ -968,6 +1021,8 @@ def wl_pir(c: Ctx) -> dict:
     nk = a.batch * W if weak else a.batch
     d_db, lo, hi = pir_setup(c, W)
     ka, result, t_wall, k_ms = pir_time(c, W, d_db, lo, hi, nk, a.steps, a.warmup)
+    if c.rank == 0:
+        c.dump("pir_answers", result["ans"])                 # after the gather + XOR: the same on every rank
     if a.check and c.rank == 0 and W == c.world:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
@@ -1035,12 +1090,13 @@ def sub_workloads(c: Ctx) -> dict:
     """BASELINE configs[2..4] measured in the same process after the
     headline's timed region, each through its own timed loop (barrier +
     synchronize, max over ranks): compact forms of the --workload eval /
-    split / pir lines, so the default run (what the driver records) shows all
-    four GPU configs.  Their CPU baselines are added by finalize()."""
+    split / pir lines, so a --full run shows all four GPU configs.  Their CPU
+    baselines are added by finalize()."""
     a = c.args
     saved = dict(vars(a))
     a.steps, a.warmup = min(a.steps, 20), min(a.warmup, 5)
     a.no_api, a.no_sweep, a.emulate_world = True, True, 1
+    a.dump_outputs = None                       # --dump-outputs is the headline's output alone
     out = {}
     # At N > 1 the PIR server is also timed in its weak form (--batch queries
     # per GPU): at N = 1 it is the same run as "pir".
@@ -1136,18 +1192,24 @@ def main() -> None:
                     help="split/pir on 1 GPU: time rank 0's share of a W-way split")
     ap.add_argument("--event-every", type=int, default=10,
                     help="record kernel timing events on every n-th timed step (1 = every step, 0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baselines, the other AES back end, "
+                         "host-buffer API rates, the configs[2..4] sub-lines, the PIR batch sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output (a fixed sample of a large one) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--aes", choices=["ttable", "bitsliced"], default=None,
                     help="tree-kernel AES back end for the headline (default: the library's)")
-    ap.add_argument("--no-variants", action="store_true", help="skip timing the other AES back end")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip timing the other AES back end")
     ap.add_argument("--pipelined", action="store_true",
                     help="evalfull: also time batches alternating over two streams (reported as 'pipelined')")
-    ap.add_argument("--no-api", action="store_true", help="skip the host-buffer (PCIe-inclusive) API rates")
-    ap.add_argument("--no-sweep", action="store_true", help="pir: skip the B in {1,16,64,256} batch sweep")
+    ap.add_argument("--no-api", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) API rates")
+    ap.add_argument("--no-sweep", action="store_true", help="pir --full: skip the B in {1,16,64,256} batch sweep")
     ap.add_argument("--strong", action="store_true",
                     help="evalfull: split a fixed --nkeys over the ranks (strong scaling) instead of --nkeys per rank")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="evalfull: skip the configs[2..4] sub-lines (workloads) of the default run")
+                    help="evalfull --full: skip the configs[2..4] sub-lines (workloads)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--spinup", type=float, default=0.5,
                     help="seconds of untimed steps before the warmup (GPU clock ramp); 0 disables")
@@ -1155,6 +1217,9 @@ def main() -> None:
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/collective plumbing only (gloo, no GPU): what the CPU tests run")
     args = ap.parse_args()
+    if not args.full:
+        # A plain run times the headline's steps and nothing else.
+        args.no_cpu_baseline = args.no_variants = args.no_api = args.no_sweep = args.no_workloads = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))

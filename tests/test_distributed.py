@@ -102,7 +102,7 @@ def test_bench_gpus_flag_spawns_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     def run(*extra):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--full",
                             "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.3", *extra],
                            capture_output=True, text=True, env=env, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -111,7 +111,7 @@ def test_bench_gpus_flag_spawns_ranks():
         return json.loads(lines[0])
     d = run()
     assert d["n_gpus"] == 2 and d["dry_run"] and d["local_ranks"] == "2"
-    # N > 1 lines keep the CPU baseline (rank 0, after the timed region) ...
+    # N > 1 --full lines keep the CPU baseline (rank 0, after the timed region) ...
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] == "port"
     # ... and report HBM traffic only where a PMC profile measured that
@@ -125,6 +125,23 @@ def test_bench_gpus_flag_spawns_ranks():
     assert p["scaling"] == "strong"
     w = run("--workload", "pir", "--pir-per-gpu", "--no-cpu-baseline")
     assert w["scaling"] == "weak"
+
+
+def test_bench_plain_run_leaves_baselines_to_full():
+    """Without --full the line carries the headline and its roofline only:
+    no CPU baseline is timed (dry run: the same finalize() as a real run)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run",
+                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["dry_run"] and "roofline" in d and "cpu_baseline" not in d
 
 
 @pytest.mark.parametrize("workload", ["evalfull", "pir"])
