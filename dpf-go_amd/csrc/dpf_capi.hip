@@ -1173,6 +1173,106 @@ int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_strid
     return DPF_OK;
 }
 
+// ---- records of rec_bytes = 32 C bytes over the wide sliced layout --------
+static int check_rec_bytes(size_t rec_bytes) {
+    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES)
+        return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 32, at most DPF_PIR_MAX_REC_BYTES");
+    return DPF_OK;
+}
+
+size_t dpf_pir_db_sliced_size_wide(uint64_t nrec, size_t rec_bytes) {
+    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES) return 0;
+    return std::max<size_t>(16, dpfk::pir_sliced_bytes_wide(nrec, rec_bytes));
+}
+
+int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                              void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_slice_db_wide(d_db, nrec, rec_bytes, d_dbs, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                 void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (rec_bytes == 32) return dpf_xor_fold_sliced_dev(device, d_bits, bits_stride, nkeys, d_dbs, nrec, d_ans, d_work, stream);
+    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
+    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
+    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0 || (uintptr_t)d_work % 16 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
+        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    if (nkeys == 0) return DPF_OK;
+    HIP_TRY(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, rec_bytes,
+                                              (uint32_t)nkeys, (uint32_t*)d_ans, (uint32_t*)d_work,
+                                              (hipStream_t)stream));
+    return DPF_OK;
+}
+
+// The split path of the 32-byte PIR entries (tree launch, then the fold) for
+// any record width; sliced: the wide matrix-core fold, else the LDS fold over
+// the row-major DB.  The fused kernel is 32-byte only and is never used here.
+static int pir_answer_wide(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                           uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
+                           uint8_t* d_ans, void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (int rc = check_key(klen, logN)) return rc;
+    const uint32_t stop = stop_of(logN);
+    if (prefix_bits > stop || (prefix >> prefix_bits) != 0) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
+    if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
+    if (int rc = check_pir_bufs(d_keys, nkeys, d_db, nrec, d_ans, d_work)) return rc;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (nkeys == 0) return DPF_OK;
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        return DPF_OK;
+    }
+    // [tree workspace | selection bits = EvalFull bytes of the subtree | fold partials]
+    uint8_t* bits = (uint8_t*)d_work + align256(tree_ws_bytes(nkeys, stop, prefix_bits, nkeys));
+    const uint64_t per_key = (uint64_t)16 << (stop - prefix_bits);
+    const bool bs = want_bs();
+    bool expanded = false;
+    forget_expanded(d_work);
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs, &expanded));
+    if (expanded) note_expanded(d_work, nkeys, stop, bs);
+    uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
+    if (sliced)
+        HIP_TRY(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes,
+                                                  (uint32_t)nkeys, (uint32_t*)d_ans, parts, st));
+    else
+        HIP_TRY(dpfk::launch_pir_fold((const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes, (uint32_t)nkeys,
+                                      (uint32_t*)d_ans, parts, st));
+    return DPF_OK;
+}
+
+int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                                   uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                                   size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
+    if (rec_bytes == 32)
+        return dpf_pir_answer_sliced_dev(device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, d_ans, d_work,
+                                         stream);
+    return pir_answer_wide(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, rec_bytes, d_ans,
+                           d_work, stream);
+}
+
+int dpf_pir_answer_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                            uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
+                            uint8_t* d_ans, void* d_work, void* stream) {
+    if (rec_bytes == 32)
+        return dpf_pir_answer_dev(device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, d_ans, d_work, stream);
+    return pir_answer_wide(false, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, rec_bytes, d_ans,
+                           d_work, stream);
+}
+
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
 
 int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
@@ -1203,6 +1303,7 @@ int dpf_xor_fold_dev(int device, const uint8_t* d_bits, size_t bits_stride, size
 struct PirDb {
     uint32_t logN = 0, pbits = 0;
     uint64_t nrec = 0;
+    size_t rec_bytes = 32;
     bool sliced = true;            // shards in the bit-sliced layout (the matrix-core fold)
     DevList devs;                  // per shard: its device
     std::vector<void*> shard;      // per device: its DB slice
@@ -1216,8 +1317,19 @@ struct PirDb {
 };
 
 int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus, void** handle) {
+    return dpf_pir_db_create_wide(db, nrec, 32, logN, ngpus, handle);
+}
+
+size_t dpf_pir_db_rec_bytes(void* handle) { return handle ? ((PirDb*)handle)->rec_bytes : 0; }
+
+// Upload chunk of a sliced shard: whole super-groups, at most this many bytes.
+constexpr uint64_t kPirUploadChunk = 256ull << 20;
+
+int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
+                           void** handle) {
     if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
     *handle = nullptr;
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
     if (logN > 63 || (logN < 64 && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: DB larger than 2^logN");
     int have = 0;
     const DevList devs = pick_devs(0, &have);
@@ -1231,6 +1343,7 @@ int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus
     h->logN = logN;
     h->pbits = pb;
     h->nrec = nrec;
+    h->rec_bytes = rec_bytes;
     // DPF_PIR_FOLD=lds keeps the row-major shards and the LDS fold (A/B runs).
     static const bool lds = [] {
         const char* e = getenv("DPF_PIR_FOLD");
@@ -1243,23 +1356,34 @@ int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus
         const uint64_t hi = std::min<uint64_t>(nrec, lo + slice);
         DeviceGuard gd(devs[(size_t)g]->id);
         void* p = nullptr;
-        const size_t bytes = h->sliced ? dpf_pir_db_sliced_size(hi - lo) : std::max<uint64_t>(hi - lo, 1) * 32;
+        const size_t bytes = h->sliced ? dpf_pir_db_sliced_size_wide(hi - lo, rec_bytes)
+                                       : std::max<uint64_t>(hi - lo, 1) * rec_bytes;
         if (hipMalloc(&p, bytes) != hipSuccess) return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
         h->devs.push_back(devs[(size_t)g]);     // ~PirDb frees what was allocated so far
         h->shard.push_back(p);
         h->shard_n.push_back(hi - lo);
         if (hi <= lo) continue;
         if (!h->sliced) {
-            if (hipMemcpy(p, db + lo * 32, (hi - lo) * 32, hipMemcpyHostToDevice) != hipSuccess)
+            if (hipMemcpy(p, db + lo * rec_bytes, (hi - lo) * rec_bytes, hipMemcpyHostToDevice) != hipSuccess)
                 return fail(DPF_ERR_HIP, "dpf: DB upload failed");
             continue;
         }
-        // Row-major records up through a staging buffer, sliced once on the device.
+        // Row-major records up through a bounded staging buffer, in chunks of
+        // whole super-groups, each sliced into its place in the shard (a
+        // chunk that starts at a multiple of 256 records is a contiguous
+        // sub-range of the sliced layout).
+        const uint64_t chunk = std::max<uint64_t>(256, kPirUploadChunk / rec_bytes / 256 * 256);
         void* tmp = nullptr;
-        if (hipMalloc(&tmp, (hi - lo) * 32) != hipSuccess) return fail(DPF_ERR_NOMEM, "dpf: DB staging allocation failed");
-        const bool ok = hipMemcpy(tmp, db + lo * 32, (hi - lo) * 32, hipMemcpyHostToDevice) == hipSuccess &&
-                        dpfk::launch_slice_db((const uint8_t*)tmp, hi - lo, (uint8_t*)p, nullptr) == hipSuccess &&
-                        hipDeviceSynchronize() == hipSuccess;
+        if (hipMalloc(&tmp, std::min<uint64_t>(hi - lo, chunk) * rec_bytes) != hipSuccess)
+            return fail(DPF_ERR_NOMEM, "dpf: DB staging allocation failed");
+        bool ok = true;
+        for (uint64_t r0 = lo; ok && r0 < hi; r0 += chunk) {
+            const uint64_t n = std::min<uint64_t>(chunk, hi - r0);
+            ok = hipMemcpy(tmp, db + r0 * rec_bytes, n * rec_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+                 dpfk::launch_slice_db_wide((const uint8_t*)tmp, n, rec_bytes, (uint8_t*)p + (r0 - lo) * rec_bytes,
+                                            nullptr) == hipSuccess &&
+                 hipDeviceSynchronize() == hipSuccess;   // tmp is reused by the next chunk
+        }
         (void)hipFree(tmp);
         if (!ok) return fail(DPF_ERR_HIP, "dpf: DB upload failed");
     }
@@ -1272,7 +1396,8 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
     if (int rc = check_key(klen, h->logN)) return rc;
     const int g = (int)h->shard.size();
-    std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * 32));
+    const size_t rb = h->rec_bytes;
+    std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * rb));
     int rc = shard((size_t)g, g, [&](int dev, size_t lo, size_t hi) {
         (void)hi;
         Dev& d = *h->devs[(size_t)dev];
@@ -1280,20 +1405,21 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
         DeviceGuard gd(d.id);
         HIP_TRY(hipError_t(d.keys.ensure(std::max<size_t>(1, nkeys * klen))));
         HIP_TRY(hipError_t(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits))));
-        HIP_TRY(hipError_t(d.out.ensure(std::max<size_t>(32, nkeys * 32))));
+        HIP_TRY(hipError_t(d.out.ensure(std::max<size_t>(32, nkeys * rb))));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
-        int r = (h->sliced ? dpf_pir_answer_sliced_dev : dpf_pir_answer_dev)(
+        // (rec_bytes == 32: the _wide entries are the 32-byte entries.)
+        int r = (h->sliced ? dpf_pir_answer_sliced_wide_dev : dpf_pir_answer_wide_dev)(
             d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)h->shard[lo],
-            h->shard_n[lo], (uint8_t*)d.out.p, d.work.p, d.st);
+            h->shard_n[lo], rb, (uint8_t*)d.out.p, d.work.p, d.st);
         if (r) return r;
-        HIP_TRY(hipMemcpyAsync(part[lo].data(), d.out.p, nkeys * 32, hipMemcpyDeviceToHost, d.st));
+        HIP_TRY(hipMemcpyAsync(part[lo].data(), d.out.p, nkeys * rb, hipMemcpyDeviceToHost, d.st));
         HIP_TRY(hipStreamSynchronize(d.st));
         return DPF_OK;
     });
     if (rc) return rc;
-    memset(ans, 0, nkeys * 32);
+    memset(ans, 0, nkeys * rb);
     for (int i = 0; i < g; ++i)
-        for (size_t b = 0; b < nkeys * 32; ++b) ans[b] ^= part[(size_t)i][b];
+        for (size_t b = 0; b < nkeys * rb; ++b) ans[b] ^= part[(size_t)i][b];
     return DPF_OK;
 }
 

@@ -1507,6 +1507,367 @@ hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, 
     return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// Records wider than 32 bytes on the matrix cores.  A record of rec_bytes =
+// 32 C bytes is C 32-byte columns, and the sliced layout gains a column index
+// between the super-group and the bit position:
+//   dbs[S][c][n][g] (u32), c < C; bit j = bit n of bytes [32c, 32c + 32) of
+//   record 256 S + 32 g + j
+// (C = 1 is the layout above, byte for byte).  To the fold a wide record is a
+// record of 8 C bit tiles instead of 8: tile T = 8c + n/32 of super-group S
+// starts at u32 (S * 8C + T) * 256, and a selection operand is the same for
+// every tile.  k_fold_mfma_w is k_fold_mfma with that one change of address:
+// a workgroup takes a column group of CG columns (CG * NS waves, NS = 8 / NT: wave wv
+// folds bit slice wv % NS of column wv / NS of the group), so
+//   - a staged block's selection rows are loaded and written to LDS once for
+//     all CG columns (selection bytes per DB byte 1 / (4 CG), from 1 / 4);
+//   - the workgroup's DB stream is runs of CG * 8 KiB, one per super-group.
+// Column groups are the grid's y dimension: every workgroup of a launch holds
+// a (super-group run, column group) pair, workgroups per launch x * y <= the
+// workgroup cap, and one k_xor_parts launch combines
+//   parts[x][key][8 CG y words]
+// into the answers.  CG is the largest of 4, 2, 1 that divides C, capped by
+// what the tile shape's registers allow (launch_pir_fold_sliced_wide).
+// WPE: the waves per SIMD the shape is compiled for (its register budget).
+template <int MT, int NT, int SG, int CG, bool NTDB, int WPE>
+__global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma_w(
+    const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
+    uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
+    uint64_t wlim, uint32_t ncols, uint32_t cg0) {
+    constexpr int NS = 8 / NT;                                 // bit slices of a column
+    constexpr int NW = NS * CG;
+    constexpr bool SC = DPF_FOLD_SEL_CHEAP >= 0 ? DPF_FOLD_SEL_CHEAP == 1 : NT < MT;
+    constexpr int kRows = 32 * MT;
+    constexpr int kRow = SG * 8 + 4;                           // words per staged row (+4: conflict-free b128 reads)
+    constexpr int kPieces = kRows * (SG * 2);                  // uint4 pieces per staged block
+    constexpr int kPer = (kPieces + 64 * NW - 1) / (64 * NW);  // per thread
+    __shared__ __attribute__((aligned(16))) uint32_t s_sel[kRows * kRow];
+    zero_answers(blockIdx.y == 0 ? zero : nullptr, zero_words);
+    const uint32_t l = threadIdx.x & 63, h = l >> 5, r = l & 31;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t w = wv % NS, cw = wv / NS;                   // bit slice, column of the group
+    const uint64_t col = (uint64_t)(cg0 + blockIdx.y) * CG + cw;
+    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
+    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
+    if (s0 >= s1) return;                                       // uniform over the workgroup
+    auto load_sel = [&](uint64_t sb, uint4 (&v)[kPer]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
+            const uint32_t row = p / (2 * SG), q = p % (2 * SG);
+            const uint64_t word = sb * 8 + 4 * q;
+            const bool ok = p < (uint32_t)kPieces && row < nkeys && word + 4 <= wlim;
+            const uint4 x = *reinterpret_cast<const uint4*>(bits + (ok ? (uint64_t)row * wpk + word : 0));
+            v[i] = ok ? x : make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto store_sel = [&](const uint4 (&v)[kPer]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
+            if (p < (uint32_t)kPieces) *reinterpret_cast<uint4*>(&s_sel[(p / (2 * SG)) * kRow + 4 * (p % (2 * SG))]) = v[i];
+        }
+    };
+    // DB pieces of a whole block (clamped past the range; never folded).
+    auto load_db = [&](uint64_t sb, uint4 (&B)[SG][NT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int sl = 0; sl < SG; ++sl) {
+            const uint64_t S = sb + sl < s1 ? sb + sl : s1 - 1;
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                B[sl][j] = fold_ld<NTDB>(&dbs[((S * ncols + col) * 256 + 32u * (w * NT + j) + r) * 2 + h]);
+        }
+    };
+    fold_v16f acc[MT][NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.0f;
+    // One super-group: 4 K-blocks of 64 records x MT x NT MFMAs.
+    auto fold_sg = [&](int sl, const uint4 (&B)[NT]) __attribute__((always_inline)) {
+        uint4 A[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            A[m] = *reinterpret_cast<const uint4*>(&s_sel[(32 * m + r) * kRow + 8 * sl + 4 * h]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            fold_v8i bo[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) bo[j] = fp4_db<SC>(u4w(B[j], t));
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const fold_v8i ao = fp4_sel<SC>(u4w(A[m], t));
+#pragma unroll
+                for (int j = 0; j < NT; ++j)
+                    acc[m][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bo[j], acc[m][j], kFoldFp4, kFoldFp4,
+                                                                               0, kE8M0One, 0, kE8M0One);
+            }
+        }
+    };
+    uint4 sv[kPer];
+    uint4 BA[SG][NT], BB[SG][NT];
+    load_sel(s0, sv);
+    load_db(s0, BA);
+    // One staged block, as in k_fold_mfma: its selection rows to LDS, the
+    // next block's loads issued, then its super-groups folded.
+    auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bn)[SG][NT]) __attribute__((always_inline)) {
+        fold_prio(sb - s0, s1 - s0);
+        lds_barrier();                                          // previous block's operand reads are done
+        store_sel(sv);
+        lds_barrier();
+        const uint64_t nb = sb + SG < s1 ? sb + SG : sb;        // next block (clamped)
+        load_sel(nb, sv);
+        load_db(nb, Bn);
+        const uint64_t n = s1 - sb;
+#pragma unroll
+        for (int sl = 0; sl < SG; ++sl)
+            if ((uint64_t)sl < n) fold_sg(sl, Bc[sl]);
+    };
+    uint64_t sb = s0;
+    for (; sb + SG < s1; sb += 2 * SG) {
+        block(sb, BA, BB);
+        block(sb + SG, BB, BA);
+    }
+    if (sb < s1) block(sb, BA, BB);
+    // Parities -> answer words: parts[x][key][8 CG y] (word = 8 * column of the launch + bit tile).
+    constexpr uint32_t pkeys = 32 * MT;
+    const uint32_t pwords = 8u * CG * gridDim.y;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            uint32_t out = 0;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const uint32_t p = ((uint32_t)acc[m][j][e]) & 1u;
+                const uint64_t b = __builtin_amdgcn_ballot_w64(p != 0);
+                const uint32_t row0 = (e & 3) + 8 * (e >> 2);
+                out = l == row0 ? (uint32_t)b : out;
+                out = l == row0 + 4 ? (uint32_t)(b >> 32) : out;
+            }
+            if (l < 32)
+                parts[((uint64_t)blockIdx.x * pkeys + 32 * m + l) * pwords + (blockIdx.y * CG + cw) * 8 + w * NT + j] = out;
+        }
+}
+
+// The wide sliced layout from a row-major DB of 32 C-byte records: k_slice_db
+// with a column index.  Workgroup b = (super-group S, column c) = (b / C,
+// b % C); its 4 waves take 64 records each.
+__global__ __launch_bounds__(256) void k_slice_db_w(const uint4* __restrict__ db, uint64_t nrec, uint32_t ncols,
+                                                     uint32_t* __restrict__ dbs) {
+    const uint64_t S = blockIdx.x / ncols;
+    const uint32_t c = blockIdx.x % ncols;
+    const uint32_t l = threadIdx.x & 63, wq = threadIdx.x >> 6;
+    const uint64_t rec = S * 256 + wq * 64 + l;
+    uint4 a = make_uint4(0, 0, 0, 0), b = a;
+    if (rec < nrec) {
+        a = db[rec * 2 * ncols + 2 * c];
+        b = db[rec * 2 * ncols + 2 * c + 1];
+    }
+    const uint32_t wd[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const uint32_t g = 2 * wq + (l >> 5);
+#pragma unroll
+    for (int wi = 0; wi < 8; ++wi) {
+        uint32_t out = 0;
+#pragma unroll
+        for (int bb = 0; bb < 32; ++bb) {
+            const uint64_t m = __builtin_amdgcn_ballot_w64(((wd[wi] >> bb) & 1u) != 0);
+            out = l == (uint32_t)bb ? (uint32_t)m : out;
+            out = l == (uint32_t)bb + 32 ? (uint32_t)(m >> 32) : out;
+        }
+        dbs[((S * ncols + c) * 256 + 32 * wi + (l & 31)) * 8 + g] = out;
+    }
+}
+
+// One key over the wide sliced DB: k_fold_sliced_direct<1> with a column
+// index.  Workgroup (x, y) folds super-group run x of column y; thread n owns
+// bit position n of that column.  parts[x][8 C words].
+__global__ __launch_bounds__(256) void k_fold_sliced_direct_w(const uint32_t* __restrict__ bits,
+                                                              const uint4* __restrict__ dbs, uint64_t nsg,
+                                                              uint64_t sg_per_block, uint32_t* __restrict__ parts,
+                                                              uint32_t* __restrict__ zero, uint64_t zero_words,
+                                                              uint64_t wlim, uint32_t ncols, uint32_t c0) {
+    zero_answers(blockIdx.y == 0 ? zero : nullptr, zero_words);
+    const uint32_t n = threadIdx.x, l = n & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t col = c0 + blockIdx.y;
+    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
+    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
+    uint32_t acc = 0;
+    auto fold = [&](uint64_t S, const uint4& a, const uint4& b) __attribute__((always_inline)) {
+        const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        if (8 * S + 8 <= wlim) {                               // uniform
+#pragma unroll
+            for (int g = 0; g < 8; ++g) acc = xam(acc, x[g], bits[8 * S + g]);
+        } else {                                               // the key row ends inside this super-group
+#pragma unroll
+            for (int g = 0; g < 8; ++g)
+                if (8 * S + g < wlim) acc = xam(acc, x[g], bits[8 * S + g]);
+        }
+    };
+    auto at = [&](uint64_t S) { return &dbs[((S * ncols + col) * 256 + n) * 2]; };
+    uint64_t S = s0;
+    for (; S + 1 < s1; S += 2) {
+        const uint4 a0 = at(S)[0], b0 = at(S)[1];
+        const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
+        fold(S, a0, b0);
+        fold(S + 1, a1, b1);
+    }
+    if (S < s1) fold(S, at(S)[0], at(S)[1]);
+    const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc) & 1) != 0);
+    if (l < 2)
+        parts[(uint64_t)blockIdx.x * (8u * gridDim.y) + 8 * blockIdx.y + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
+}
+
+uint64_t pir_sliced_bytes_wide(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * 256 * rec_bytes; }
+
+hipError_t launch_slice_db_wide(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st) {
+    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > kFoldMaxRecBytes) return hipErrorInvalidValue;
+    if (rec_bytes == 32) return launch_slice_db(db, nrec, dbs, st);
+    const uint64_t nsg = (nrec + 255) / 256, C = rec_bytes / 32;
+    if (nsg == 0) return hipSuccess;
+    // One workgroup per (super-group, column), in launches of at most 2^30.
+    const uint64_t per = (1ull << 30) / C;
+    for (uint64_t S0 = 0; S0 < nsg; S0 += per) {
+        const uint64_t n = nsg - S0 < per ? nsg - S0 : per;
+        hipLaunchKernelGGL(k_slice_db_w, dim3((uint32_t)(n * C)), dim3(256), 0, st,
+                           reinterpret_cast<const uint4*>(db + S0 * 256 * rec_bytes), nrec - S0 * 256, (uint32_t)C,
+                           reinterpret_cast<uint32_t*>(dbs + S0 * 256 * rec_bytes));
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+namespace {
+// One key group (<= 32 MT keys) over the wide sliced DB, as launch_mfma_mt:
+// launches of x * y <= cap workgroups (x super-group runs of <= msg
+// super-groups, y column groups), each followed by one k_xor_parts.
+template <int MT, int NT, int SG, int CG, int WPE>
+hipError_t launch_mfma_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C, uint32_t nk,
+                         uint32_t* parts, uint32_t* ans, uint32_t* zero, uint64_t zero_words, hipStream_t st) {
+    constexpr int NW = 8 / NT * CG;
+    static_assert(32 * MT * CG * 32 <= (int)kFoldPartBytes, "a workgroup's partial fits its 16 KiB");
+    static int per_cu = [] {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma_w<MT, NT, SG, CG, false, WPE>, 64 * NW, 0) !=
+                hipSuccess || n < 1)
+            n = 1;
+        return n;
+    }();
+    const uint64_t cap = g_fold_blocks.load(std::memory_order_relaxed);
+    const uint64_t msg = (uint64_t)fold_max_sg() / SG * SG > 0 ? (uint64_t)fold_max_sg() / SG * SG : SG;
+    const bool ntdb = nsg * 256 * 32 * C >= fold_nt_min_bytes();   // by DB bytes
+    const uint64_t ncg = C / CG;
+    const uint64_t gy_max = ncg < cap ? ncg : cap;
+    const uint64_t resident = (uint64_t)cu_count_fold() * (uint64_t)per_cu;
+    for (uint64_t g0 = 0; g0 < ncg; g0 += gy_max) {
+        const uint64_t gy = ncg - g0 < gy_max ? ncg - g0 : gy_max;
+        const uint64_t xcap = cap / gy;                          // >= 1
+        const uint64_t per_pass = xcap * msg;
+        for (uint64_t S0 = 0; S0 < nsg; S0 += per_pass) {
+            const uint64_t n = nsg - S0 < per_pass ? nsg - S0 : per_pass;
+            uint64_t want = (n + msg - 1) / msg;                 // none folds more than msg super-groups
+            if (want < resident / gy) want = resident / gy;
+            if (want < 1) want = 1;
+            uint64_t blocks, spb;
+            split_chunks(n, want, SG, blocks, spb, xcap);
+            if (spb > msg || blocks * gy > cap) return hipErrorInvalidValue;
+            const uint32_t* b = bits + S0 * 8;
+            const uint64_t wlim = wpk > S0 * 8 ? wpk - S0 * 8 : 0;
+            const uint4* d = reinterpret_cast<const uint4*>(dbs + S0 * 256 * 32 * C);
+            const bool first = g0 == 0 && S0 == 0;
+            uint32_t* z = first ? zero : nullptr;
+            const uint64_t zw = first ? zero_words : 0;
+            const dim3 grid((uint32_t)blocks, (uint32_t)gy);
+            if (ntdb)
+                hipLaunchKernelGGL((k_fold_mfma_w<MT, NT, SG, CG, true, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
+                                   nk, spb, parts, z, zw, wlim, C, (uint32_t)g0);
+            else
+                hipLaunchKernelGGL((k_fold_mfma_w<MT, NT, SG, CG, false, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
+                                   nk, spb, parts, z, zw, wlim, C, (uint32_t)g0);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            if (hipError_t e = launch_xor_parts(parts, blocks, nk, 32u * MT, (uint32_t)(8 * CG * gy), ans, 8ull * C,
+                                                (uint32_t)(8 * CG * g0), st);
+                e != hipSuccess)
+                return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// One key over the wide sliced DB (k_fold_sliced_direct_w): x * y <= cap.
+hipError_t launch_sliced_direct_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C,
+                                  uint32_t* parts, uint32_t* ans, hipStream_t st) {
+    const uint64_t cap = g_fold_blocks.load(std::memory_order_relaxed);
+    // parts[x][8 C words] of a launch: x * y * 32 bytes, far inside the partials area.
+    const uint64_t gy_max = C < cap ? C : cap;
+    // (Default loads, as k_fold_sliced_direct: nontemporal ones measured slower for it.)
+    for (uint64_t c0 = 0; c0 < C; c0 += gy_max) {
+        const uint64_t gy = C - c0 < gy_max ? C - c0 : gy_max;
+        uint64_t want = (uint64_t)cu_count_fold() * 8 / gy;
+        if (want < 1) want = 1;
+        uint64_t blocks, spb;
+        split_chunks(nsg, want, 2, blocks, spb, cap / gy);
+        if (blocks * gy > cap) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_fold_sliced_direct_w, dim3((uint32_t)blocks, (uint32_t)gy), dim3(256), 0, st, bits,
+                           reinterpret_cast<const uint4*>(dbs), nsg, spb, parts, c0 == 0 ? ans : nullptr,
+                           c0 == 0 ? 8ull * C : 0ull, wpk, C, (uint32_t)c0);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        if (hipError_t e = launch_xor_parts(parts, blocks, 1u, 1u, (uint32_t)(8 * gy), ans, 8ull * C, (uint32_t)(8 * c0), st);
+            e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+}  // namespace
+
+hipError_t launch_pir_fold_sliced_wide(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
+                                       uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts,
+                                       hipStream_t st) {
+    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > kFoldMaxRecBytes) return hipErrorInvalidValue;
+    // 32-byte records: exactly the launches of the 32-byte entry.
+    if (rec_bytes == 32) return launch_pir_fold_sliced(bits, words_per_key, dbs, nrec, nkeys, ans, parts, st);
+    if (nkeys == 0) return hipSuccess;
+    if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, st);
+    if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
+    const uint64_t nsg = (nrec + 255) / 256;
+    const uint32_t C = (uint32_t)(rec_bytes / 32);
+    if (nkeys <= (uint32_t)DPF_FOLD_SLICED_DIRECT)
+        return launch_sliced_direct_w(bits, words_per_key, dbs, nsg, C, parts, ans, st);
+    // Columns per workgroup: the largest of 4, 2, 1 that divides C, capped
+    // per tile shape below.  DPF_FOLD_WIDE_CG=<1|2|4> (measurement) caps it.
+    static const int cg_env = [] {
+        const char* e = getenv("DPF_FOLD_WIDE_CG");
+        return e && atoi(e) > 0 ? atoi(e) : 4;
+    }();
+    int cg = C % 4 == 0 ? 4 : C % 2 == 0 ? 2 : 1;
+    if (cg > cg_env) cg = cg_env >= 2 ? 2 : 1;
+    for (uint32_t k0 = 0; k0 < nkeys; k0 += 256) {
+        const uint32_t nk = nkeys - k0 < 256 ? nkeys - k0 : 256;
+        const uint32_t* b = bits + (uint64_t)k0 * words_per_key;
+        uint32_t* zero = k0 == 0 ? ans : nullptr;
+        const uint64_t zw = k0 == 0 ? (uint64_t)nkeys * 8 * C : 0;
+        uint32_t* a = ans + (uint64_t)k0 * 8 * C;
+        hipError_t e;
+#define DPF_MW(MT_, NT_, SG_, CG_, WPE_) \
+    launch_mfma_w<MT_, NT_, SG_, CG_, WPE_>(b, words_per_key, dbs, nsg, C, nk, parts, a, zero, zw, st)
+        // Tile shapes as launch_pir_fold_sliced.  A column group of CG
+        // columns is 4 CG waves, so the shape has 512 / CG registers (less
+        // where two workgroups share a CU): the staged blocks shrink (SG)
+        // until nothing spills, and CG stops where that no longer works
+        // (register counts per instantiation: DESIGN §4.4).
+        if (nk <= 32) e = cg == 4 ? DPF_MW(1, 2, 2, 4, 4) : cg == 2 ? DPF_MW(1, 2, 2, 2, 4) : DPF_MW(1, 2, 4, 1, 2);
+        else if (nk <= 64) e = DPF_MW(2, 2, 2, 1, 2);   // CG = 2 (<2,2,4,2>, 2 waves per SIMD) measured no faster
+        else if (nk <= 128) e = cg >= 2 ? DPF_MW(4, 2, 2, 2, 2) : DPF_MW(4, 2, 4, 1, 1);
+        else e = DPF_MW(8, 2, 4, 1, 1);
+#undef DPF_MW
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 #ifndef DPF_PIR_FUSED_KERNEL
 #define DPF_PIR_FUSED_KERNEL 0   // k_pir_fused is built only in the experimental build (make experimental)
 #endif

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #define DPF_FOLD_PLAN 1   // plan_fold() below (tools/fold_bench.hip)
+#define DPF_FOLD_WIDE 1   // the _wide launchers below (tools/fold_bench.hip)
 
 namespace dpfk {
 
@@ -40,6 +41,20 @@ hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint8_t* dbs, hipSt
 hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
                                   uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st,
                                   uint32_t sgm_keys = 0, uint32_t sgm_g = 1);
+
+// The same for records of rec_bytes = 32 C bytes (a positive multiple of 32,
+// at most kFoldMaxRecBytes): the wide sliced layout dbs[S][c][n][g], column
+// c < C between the super-group and the bit position (C = 1: the layout
+// above), pir_sliced_bytes_wide(nrec, rec_bytes) bytes.  launch_slice_db_wide
+// of records [256 S0, ...) into dbs + S0 * 256 * rec_bytes writes what
+// slicing the whole DB writes there.  ans is [nkeys][rec_bytes]; bits / parts
+// as above.  rec_bytes == 32 makes exactly the 32-byte launchers' launches.
+constexpr uint64_t kFoldMaxRecBytes = 32768;
+uint64_t pir_sliced_bytes_wide(uint64_t nrec, uint64_t rec_bytes);
+hipError_t launch_slice_db_wide(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st);
+hipError_t launch_pir_fold_sliced_wide(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
+                                       uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts,
+                                       hipStream_t st);
 
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per

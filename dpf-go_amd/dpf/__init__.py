@@ -100,6 +100,13 @@ SIGNATURES = {
     "dpf_pir_answer_sliced_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _vp, _vp, _vp]),
     "dpf_xor_fold_sliced_dev": (_int, [_int, _vp, _sz, _sz, _vp, _u64, _vp, _vp, _vp]),
     "dpf_set_fold_limits": (_int, [_u32, _u32]),
+    "dpf_pir_db_sliced_size_wide": (_sz, [_u64, _sz]),
+    "dpf_pir_db_slice_wide_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_xor_fold_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_answer_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_answer_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_db_create_wide": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
+    "dpf_pir_db_rec_bytes": (_sz, [_vp]),
     "dpf_pir_db_create": (_int, [_u8p, _u64, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_answer": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_pir_db_free": (None, [_vp]),
@@ -531,6 +538,38 @@ def xor_fold_sliced_dev(d_bits, bits_stride: int, nkeys: int, d_dbs, nrec: int, 
                                          _ptr(d_work), _stream_handle(stream)))
 
 
+def pir_db_sliced_size_wide(nrec: int, rec_bytes: int) -> int:
+    """Bytes of the wide bit-sliced layout of nrec records of rec_bytes (a multiple of 32)."""
+    return int(lib().dpf_pir_db_sliced_size_wide(nrec, rec_bytes))
+
+
+def pir_db_slice_wide_dev(d_db, nrec: int, rec_bytes: int, d_dbs, device: int = 0, stream=None) -> None:
+    """Wide bit-sliced copy dbs[S][c][n][g] of a row-major DB of rec_bytes-byte records."""
+    _check(lib().dpf_pir_db_slice_wide_dev(device, _ptr(d_db), nrec, rec_bytes, _ptr(d_dbs), _stream_handle(stream)))
+
+
+def xor_fold_sliced_wide_dev(d_bits, bits_stride: int, nkeys: int, d_dbs, nrec: int, rec_bytes: int, d_ans, d_work,
+                             device: int = 0, stream=None) -> None:
+    """xor_fold_dev over the wide bit-sliced DB (the matrix-core fold, any rec_bytes = 32 C)."""
+    _check(lib().dpf_xor_fold_sliced_wide_dev(device, _ptr(d_bits), bits_stride, nkeys, _ptr(d_dbs), nrec, rec_bytes,
+                                              _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_answer_sliced_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_dbs, nrec: int, rec_bytes: int, d_ans,
+                               d_work, prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """Server answers (nkeys x rec_bytes) over the wide bit-sliced DB slice of subtree (prefix_bits, prefix)."""
+    _check(lib().dpf_pir_answer_sliced_wide_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix,
+                                                _ptr(d_dbs), nrec, rec_bytes, _ptr(d_ans), _ptr(d_work),
+                                                _stream_handle(stream)))
+
+
+def pir_answer_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_db, nrec: int, rec_bytes: int, d_ans, d_work,
+                        prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """pir_answer_dev for rec_bytes-byte records (row-major DB, the LDS fold)."""
+    _check(lib().dpf_pir_answer_wide_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix, _ptr(d_db),
+                                         nrec, rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -540,24 +579,29 @@ def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
 
 
 class PirDB:
-    """A 32-byte-record DB resident in HBM, sharded by top-level subtree over
-    ngpus GPUs; answer() returns each key's XOR-inner-product (host XOR of
-    the per-GPU partials)."""
+    """A DB of rec_bytes-byte records (a multiple of 32; default 32 whatever
+    the array's shape) resident in HBM, sharded by top-level subtree over
+    ngpus GPUs; answer() returns each key's XOR-inner-product, (n, rec_bytes)
+    (host XOR of the per-GPU partials)."""
 
-    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1):
+    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
-        if d.size % 32:
-            raise ValueError("DB size must be a multiple of 32 bytes")
+        if rec_bytes <= 0 or d.size % rec_bytes:
+            raise ValueError("DB size must be a multiple of %d bytes" % rec_bytes)
         self.logN = logN
-        self.nrec = d.size // 32
+        self.rec_bytes = rec_bytes
+        self.nrec = d.size // rec_bytes
         h = _vp()
-        _check(lib().dpf_pir_db_create(_buf(d), self.nrec, logN, ngpus, ctypes.byref(h)))
+        if rec_bytes == 32:
+            _check(lib().dpf_pir_db_create(_buf(d), self.nrec, logN, ngpus, ctypes.byref(h)))
+        else:
+            _check(lib().dpf_pir_db_create_wide(_buf(d), self.nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
         self._h = h
 
     def answer(self, keys: np.ndarray) -> np.ndarray:
         kk = np.ascontiguousarray(keys, dtype=np.uint8)
         n, kl = kk.shape
-        ans = np.zeros((n, 32), np.uint8)
+        ans = np.zeros((n, int(lib().dpf_pir_db_rec_bytes(self._h))), np.uint8)
         _check(lib().dpf_pir_answer(self._h, _buf(kk), kl, n, _buf(ans)))
         return ans
 

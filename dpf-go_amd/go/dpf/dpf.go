@@ -128,10 +128,12 @@ func EvalBatch(keys []DPFkey, xs [][]uint64, logN uint64, ngpus int) [][]byte {
 	return out
 }
 
-// PirDB is one PIR server's database of 32-byte records on the GPUs
-// (dpf_pir_db_create): records are sharded over ngpus devices by top-level
-// subtree, and Answer returns this server's 32-byte share per query key:
-// the XOR of the records whose EvalFull bit is set (dpf.go:243-262).
+// PirDB is one PIR server's database of 32-byte records (NewPirDB) or of
+// recBytes-byte records (NewPirDBWide) on the GPUs (dpf_pir_db_create,
+// dpf_pir_db_create_wide): records are sharded over ngpus devices by
+// top-level subtree, and Answer returns this server's record-sized share per
+// query key: the XOR of the records whose EvalFull bit is set
+// (dpf.go:243-262).
 type PirDB struct {
 	h unsafe.Pointer
 }
@@ -148,7 +150,26 @@ func NewPirDB(db []byte, logN uint64, ngpus int) *PirDB {
 	return p
 }
 
-// Answer returns 32 bytes per key: keys[i]'s share of DB[alpha_i].
+// NewPirDBWide uploads db (len(db)/recBytes records of recBytes bytes, a
+// positive multiple of 32; at most 2^logN records) to ngpus GPUs.
+func NewPirDBWide(db []byte, recBytes int, logN uint64, ngpus int) *PirDB {
+	if recBytes <= 0 || recBytes%32 != 0 || len(db)%recBytes != 0 {
+		panic("dpf: PIR records are a positive multiple of 32 bytes")
+	}
+	p := &PirDB{}
+	var h unsafe.Pointer
+	check(C.dpf_pir_db_create_wide(u8(db), C.uint64_t(len(db)/recBytes), C.size_t(recBytes), C.uint32_t(logN),
+		C.int(ngpus), &h))
+	p.h = h
+	return p
+}
+
+// RecBytes is the record size of the database (dpf_pir_db_rec_bytes).
+func (p *PirDB) RecBytes() int {
+	return int(C.dpf_pir_db_rec_bytes(p.h))
+}
+
+// Answer returns RecBytes() bytes per key: keys[i]'s share of DB[alpha_i].
 func (p *PirDB) Answer(keys []DPFkey) [][]byte {
 	if len(keys) == 0 {
 		return nil
@@ -161,11 +182,12 @@ func (p *PirDB) Answer(keys []DPFkey) [][]byte {
 		}
 		copy(packed[i*kl:], k)
 	}
-	flat := make([]byte, 32*len(keys))
+	rb := p.RecBytes()
+	flat := make([]byte, rb*len(keys))
 	check(C.dpf_pir_answer(p.h, u8(packed), C.size_t(kl), C.size_t(len(keys)), u8(flat)))
 	out := make([][]byte, len(keys))
 	for i := range out {
-		out[i] = flat[i*32 : (i+1)*32 : (i+1)*32]
+		out[i] = flat[i*rb : (i+1)*rb : (i+1)*rb]
 	}
 	return out
 }

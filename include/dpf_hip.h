@@ -260,7 +260,8 @@ int dpf_xor_fold_dev(int device, const uint8_t* d_bits, size_t bits_stride, size
  * past nrec read as 0).  dpf_pir_db_slice_dev writes it from the row-major
  * DB (nrec x 32 B) into dpf_pir_db_sliced_size(nrec) bytes.  The _sliced
  * entry points take that layout and give the same answers as their row-major
- * forms (same workspace sizes); 32-byte records only. */
+ * forms (same workspace sizes); 32-byte records (wider ones: the _wide
+ * entry points below). */
 size_t dpf_pir_db_sliced_size(uint64_t nrec);
 int dpf_pir_db_slice_dev(int device, const uint8_t* d_db, uint64_t nrec, uint8_t* d_dbs, void* stream);
 int dpf_pir_answer_sliced_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
@@ -268,6 +269,45 @@ int dpf_pir_answer_sliced_dev(int device, const uint8_t* d_keys, size_t key_len,
                               uint8_t* d_ans, void* d_work, void* stream);
 int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_dbs,
                             uint64_t nrec, uint8_t* d_ans, void* d_work, void* stream);
+/* Records wider than 32 bytes on the matrix cores.  rec_bytes = 32*C, a
+ * positive multiple of 32 up to DPF_PIR_MAX_REC_BYTES (else DPF_ERR_PARAM;
+ * the size function returns 0).  The wide sliced layout is ABI:
+ *   dbs[S][c][n][g] (u32): super-group S of 256 records, column c < C, bit
+ *   position n < 256, record group g < 8; bit j of the word = bit n of bytes
+ *   [32c, 32c+32) of record 256*S + 32*g + j, bit n of a column being bit n%8
+ *   of its byte n/8.  Records past nrec read as 0.
+ * It takes ceil(nrec/256) * 256 * rec_bytes bytes (minimum 16), and for C = 1
+ * it is the 32-byte layout above, byte for byte.  Super-groups follow one
+ * another, so a shard or an upload chunk that starts at a multiple of 256
+ * records is a contiguous sub-range: slicing records [256*S0, ...) into
+ * d_dbs + S0*256*rec_bytes writes the bytes that slicing the whole DB writes
+ * there (how a DB larger than a staging buffer is loaded).
+ * The _wide entry points keep the contracts, workspace sizes and answers of
+ * their 32-byte forms with d_ans = [nkeys][rec_bytes] (overwritten), and at
+ * rec_bytes == 32 they are those forms.  dpf_xor_fold_sliced_wide_dev is
+ * dpf_xor_fold_dev over the sliced DB; dpf_pir_answer_sliced_wide_dev is the
+ * tree pass of dpf_pir_answer_sliced_dev followed by the wide fold (always
+ * the split path); dpf_pir_answer_wide_dev is dpf_pir_answer_dev for a
+ * row-major DB of rec_bytes-byte records (the LDS fold of dpf_xor_fold_dev).
+ * The fold gives a workgroup up to 4 columns of its super-groups, so the
+ * selection bits it reads per DB byte fall from 1/4 towards 1/16.  Over
+ * 512 MiB of 64-byte to 1-KiB records the sliced form measured faster than
+ * the row-major one (dpf_xor_fold_dev, dpf_pir_answer_wide_dev) at every
+ * batch size tried, 1 to 256 keys (no crossover
+ * found), so the handle below keeps its shards sliced. */
+#define DPF_PIR_MAX_REC_BYTES 32768
+size_t dpf_pir_db_sliced_size_wide(uint64_t nrec, size_t rec_bytes);
+int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                              void* stream);
+int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                 void* stream);
+int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                                   uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                                   size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream);
+int dpf_pir_answer_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                            uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
+                            uint8_t* d_ans, void* d_work, void* stream);
 /* Tuning / test limits of the XOR fold launches (process-wide; 0 = default):
  * at most max_blocks workgroups per fold launch (default and maximum 1024),
  * and at most max_sg_per_block super-groups of 256 records per matrix-core
@@ -304,6 +344,16 @@ int dpf_pir_kernel_for(size_t nkeys, uint32_t logN, uint32_t prefix_bits);
  * XORs the per-GPU partial answers (RCCL has no XOR reduction). */
 int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus, void** handle);
 int dpf_pir_answer(void* handle, const uint8_t* keys, size_t key_len, size_t nkeys, uint8_t* ans);
+/* The same for records of rec_bytes bytes (a positive multiple of 32 up to
+ * DPF_PIR_MAX_REC_BYTES, else DPF_ERR_PARAM with *handle = NULL);
+ * dpf_pir_db_create is the rec_bytes = 32 case.  The shards are kept in the
+ * wide sliced layout (row-major with env DPF_PIR_FOLD=lds), uploaded through
+ * a staging buffer of at most 256 MiB in chunks of whole super-groups.
+ * dpf_pir_answer on the handle writes nkeys * dpf_pir_db_rec_bytes(handle)
+ * bytes. */
+int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
+                           void** handle);
+size_t dpf_pir_db_rec_bytes(void* handle);
 void dpf_pir_db_free(void* handle);
 
 #ifdef __cplusplus

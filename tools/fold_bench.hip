@@ -32,7 +32,7 @@ int main(int argc, char** argv) {
     const uint32_t nkeys = argc > 1 ? (uint32_t)atoi(argv[1]) : 64;
     const uint64_t rec_bytes = argc > 2 ? (uint64_t)atoll(argv[2]) : 32;
     const uint64_t nrec = argc > 3 ? 1ull << atoi(argv[3]) : 1ull << 24;
-    const int iters = 20;
+    const int iters = getenv("FOLD_ITERS") && atoi(getenv("FOLD_ITERS")) > 0 ? atoi(getenv("FOLD_ITERS")) : 20;
     const uint64_t wpk = (nrec + 127) / 128 * 4;
     void *bits, *db, *ans, *parts;
     CK(hipMalloc(&bits, (size_t)nkeys * wpk * 4));
@@ -50,9 +50,10 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    // FOLD_MODE=mfma: the matrix-core fold over the bit-sliced DB (32-byte
-    // records), built once here as the PIR server does at load time; its
-    // answers must equal the Four-Russians / direct fold's for every key.
+    // FOLD_MODE=mfma: the matrix-core fold over the bit-sliced DB (the wide
+    // layout and fold for rec_bytes > 32), built once here as the PIR server
+    // does at load time; its answers must equal the Four-Russians / direct
+    // fold's for every key.
     const bool mfma = getenv("FOLD_MODE") && getenv("FOLD_MODE")[0] == 'm';
     // FOLD_BLOCKS=n: at most n workgroups per fold launch (dpf_set_fold_limits).
     if (getenv("FOLD_BLOCKS")) dpfk::set_fold_limits((uint32_t)atoi(getenv("FOLD_BLOCKS")), 0);
@@ -60,10 +61,17 @@ int main(int argc, char** argv) {
     float slice_ms = 0;
     std::vector<uint8_t> ref((size_t)nkeys * rec_bytes);
     if (mfma) {
+#ifdef DPF_FOLD_WIDE
+        CK(hipMalloc(&dbs, dpfk::pir_sliced_bytes_wide(nrec, rec_bytes)));
+        CK(hipEventRecord(e0, 0));
+        if (rec_bytes != 32) CK(dpfk::launch_slice_db_wide((const uint8_t*)db, nrec, rec_bytes, (uint8_t*)dbs, 0));
+        else CK(dpfk::launch_slice_db((const uint8_t*)db, nrec, (uint8_t*)dbs, 0));
+#else
         if (rec_bytes != 32) { fprintf(stderr, "mfma mode: 32-byte records only\n"); return 2; }
         CK(hipMalloc(&dbs, dpfk::pir_sliced_bytes(nrec)));
         CK(hipEventRecord(e0, 0));
         CK(dpfk::launch_slice_db((const uint8_t*)db, nrec, (uint8_t*)dbs, 0));
+#endif
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         CK(hipEventElapsedTime(&slice_ms, e0, e1));
@@ -94,6 +102,11 @@ int main(int argc, char** argv) {
         if (sgm)
             CK(dpfk::launch_pir_fold_sliced((const uint32_t*)bits_sgm, wpk, (const uint8_t*)dbs, nrec, nkeys,
                                             (uint32_t*)ans, (uint32_t*)parts, 0, nkeys, sgm_g));
+#ifdef DPF_FOLD_WIDE
+        else if (mfma && rec_bytes != 32)
+            CK(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)bits, wpk, (const uint8_t*)dbs, nrec, rec_bytes, nkeys,
+                                                 (uint32_t*)ans, (uint32_t*)parts, 0));
+#endif
         else if (mfma)
             CK(dpfk::launch_pir_fold_sliced((const uint32_t*)bits, wpk, (const uint8_t*)dbs, nrec, nkeys,
                                             (uint32_t*)ans, (uint32_t*)parts, 0));
