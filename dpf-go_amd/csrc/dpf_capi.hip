@@ -1042,37 +1042,6 @@ size_t dpf_pir_workspace_size(size_t nkeys, uint32_t logN, uint32_t prefix_bits)
            dpfk::pir_fold_parts_bytes();
 }
 
-int dpf_pir_answer_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
-                       uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, uint8_t* d_ans,
-                       void* d_work, void* stream) {
-    if (int rc = check_key(klen, logN)) return rc;
-    const uint32_t stop = stop_of(logN);
-    if (prefix_bits > stop || (prefix >> prefix_bits) != 0) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
-    const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
-    if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
-    if (int rc = check_pir_bufs(d_keys, nkeys, d_db, nrec, d_ans, d_work)) return rc;
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (nkeys == 0) return DPF_OK;
-    if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * 32, st));
-        return DPF_OK;
-    }
-    // [tree workspace | selection bits = EvalFull bytes of the subtree | fold partials]
-    uint8_t* bits = (uint8_t*)d_work + align256(tree_ws_bytes(nkeys, stop, prefix_bits, nkeys));
-    const uint64_t per_key = (uint64_t)16 << (stop - prefix_bits);
-    const bool bs = want_bs();
-    bool expanded = false;
-    forget_expanded(d_work);
-    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs, &expanded));
-    if (expanded) note_expanded(d_work, nkeys, stop, bs);
-    uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
-    HIP_TRY(dpfk::launch_pir_fold((const uint32_t*)bits, per_key / 4, d_db, nrec, 32, (uint32_t)nkeys, (uint32_t*)d_ans,
-                                  parts, st));
-    return DPF_OK;
-}
-
 // PIR kernel over the sliced DB: the tree launch then the fold launch
 // (DPF_PIR_SPLIT, the default: measured faster), or both in one launch
 // where it applies (DPF_PIR_FUSED, k_pir_fused).  DPF_PIR_KERNEL=split|
@@ -1104,123 +1073,30 @@ int dpf_pir_kernel_for(size_t nkeys, uint32_t logN, uint32_t prefix_bits) {
                : DPF_PIR_SPLIT;
 }
 
-size_t dpf_pir_db_sliced_size(uint64_t nrec) { return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec)); }
+size_t dpf_pir_db_sliced_size(uint64_t nrec) { return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec, 32)); }
 
 int dpf_pir_db_slice_dev(int device, const uint8_t* d_db, uint64_t nrec, uint8_t* d_dbs, void* stream) {
     if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
     if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
     DeviceGuard g(device);
-    HIP_TRY(dpfk::launch_slice_db(d_db, nrec, d_dbs, (hipStream_t)stream));
+    HIP_TRY(dpfk::launch_slice_db(d_db, nrec, 32, d_dbs, (hipStream_t)stream));
     return DPF_OK;
 }
 
-int dpf_pir_answer_sliced_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
-                              uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
-                              uint8_t* d_ans, void* d_work, void* stream) {
-    if (int rc = check_key(klen, logN)) return rc;
-    const uint32_t stop = stop_of(logN);
-    if (prefix_bits > stop || (prefix >> prefix_bits) != 0) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
-    const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
-    if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
-    if (int rc = check_pir_bufs(d_keys, nkeys, d_dbs, nrec, d_ans, d_work)) return rc;
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (nkeys == 0) return DPF_OK;
-    if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * 32, st));
-        return DPF_OK;
-    }
-    // The same workspace and tree pass as dpf_pir_answer_dev; the fold reads the sliced DB.
-    uint8_t* bits = (uint8_t*)d_work + align256(tree_ws_bytes(nkeys, stop, prefix_bits, nkeys));
-    const uint64_t per_key = (uint64_t)16 << (stop - prefix_bits);
-    const bool bs = want_bs();
-    const int fz = g_pir_kernel.load(std::memory_order_relaxed);
-    if (!bs && fz != DPF_PIR_SPLIT && dpfk::pir_fused_ok(nkeys, stop, prefix_bits, fz == DPF_PIR_FUSED_ANY)) {
-        // One launch: tree + matrix-core fold (k_pir_fused) from the expanded records.
-        const TreeWs w = tree_ws(d_work, nkeys, stop);
-        forget_expanded(d_work);
-        HIP_TRY(dpfk::launch_unpack(d_keys, klen, nkeys, stop, w.ek, st));
-        note_expanded(d_work, nkeys, stop, false);
-        uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
-        HIP_TRY(dpfk::launch_pir_fused(w.ek, (uint32_t)nkeys, stop, prefix_bits, prefix, d_dbs, nrec, (uint32_t*)d_ans,
-                                       parts, st));
-        return DPF_OK;
-    }
-    bool expanded = false;
-    forget_expanded(d_work);
-    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs, &expanded));
-    if (expanded) note_expanded(d_work, nkeys, stop, bs);
-    uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
-    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)bits, per_key / 4, d_dbs, nrec, (uint32_t)nkeys,
-                                         (uint32_t*)d_ans, parts, st));
-    return DPF_OK;
-}
-
-int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_dbs,
-                            uint64_t nrec, uint8_t* d_ans, void* d_work, void* stream) {
-    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
-    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
-    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0)
-        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
-        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    if (nkeys == 0) return DPF_OK;
-    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, (uint32_t)nkeys,
-                                         (uint32_t*)d_ans, (uint32_t*)d_work, (hipStream_t)stream));
-    return DPF_OK;
-}
-
-// ---- records of rec_bytes = 32 C bytes over the wide sliced layout --------
 static int check_rec_bytes(size_t rec_bytes) {
     if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES)
         return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 32, at most DPF_PIR_MAX_REC_BYTES");
     return DPF_OK;
 }
 
-size_t dpf_pir_db_sliced_size_wide(uint64_t nrec, size_t rec_bytes) {
-    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES) return 0;
-    return std::max<size_t>(16, dpfk::pir_sliced_bytes_wide(nrec, rec_bytes));
-}
-
-int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
-                              void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
-    if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    DeviceGuard g(device);
-    HIP_TRY(dpfk::launch_slice_db_wide(d_db, nrec, rec_bytes, d_dbs, (hipStream_t)stream));
-    return DPF_OK;
-}
-
-int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
-                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
-                                 void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
-    if (rec_bytes == 32) return dpf_xor_fold_sliced_dev(device, d_bits, bits_stride, nkeys, d_dbs, nrec, d_ans, d_work, stream);
-    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
-    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
-    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0 || (uintptr_t)d_work % 16 != 0)
-        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
-        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    if (nkeys == 0) return DPF_OK;
-    HIP_TRY(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, rec_bytes,
-                                              (uint32_t)nkeys, (uint32_t*)d_ans, (uint32_t*)d_work,
-                                              (hipStream_t)stream));
-    return DPF_OK;
-}
-
-// The split path of the 32-byte PIR entries (tree launch, then the fold) for
-// any record width; sliced: the wide matrix-core fold, else the LDS fold over
-// the row-major DB.  The fused kernel is 32-byte only and is never used here.
-static int pir_answer_wide(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
-                           uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
-                           uint8_t* d_ans, void* d_work, void* stream) {
+// The PIR answer of the four *_dev entries below: the subtree EvalFull into
+// the workspace (tree launch), then the fold over the DB of rec_bytes-wide
+// records -- sliced: the matrix-core fold over the bit-sliced layout, else
+// the LDS fold over the row-major DB.  In front of that, 32-byte sliced
+// records take both in one launch (k_pir_fused) where g_pir_kernel selects it.
+static int pir_answer(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                      uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
+                      uint8_t* d_ans, void* d_work, void* stream) {
     if (int rc = check_rec_bytes(rec_bytes)) return rc;
     if (int rc = check_key(klen, logN)) return rc;
     const uint32_t stop = stop_of(logN);
@@ -1239,38 +1115,104 @@ static int pir_answer_wide(bool sliced, int device, const uint8_t* d_keys, size_
     // [tree workspace | selection bits = EvalFull bytes of the subtree | fold partials]
     uint8_t* bits = (uint8_t*)d_work + align256(tree_ws_bytes(nkeys, stop, prefix_bits, nkeys));
     const uint64_t per_key = (uint64_t)16 << (stop - prefix_bits);
+    uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
     const bool bs = want_bs();
+    const int fz = g_pir_kernel.load(std::memory_order_relaxed);
+    if (sliced && rec_bytes == 32 && !bs && fz != DPF_PIR_SPLIT &&
+        dpfk::pir_fused_ok(nkeys, stop, prefix_bits, fz == DPF_PIR_FUSED_ANY)) {
+        // One launch: tree + matrix-core fold (k_pir_fused) from the expanded records.
+        const TreeWs w = tree_ws(d_work, nkeys, stop);
+        forget_expanded(d_work);
+        HIP_TRY(dpfk::launch_unpack(d_keys, klen, nkeys, stop, w.ek, st));
+        note_expanded(d_work, nkeys, stop, false);
+        HIP_TRY(dpfk::launch_pir_fused(w.ek, (uint32_t)nkeys, stop, prefix_bits, prefix, d_db, nrec, (uint32_t*)d_ans,
+                                       parts, st));
+        return DPF_OK;
+    }
     bool expanded = false;
     forget_expanded(d_work);
     HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs, &expanded));
     if (expanded) note_expanded(d_work, nkeys, stop, bs);
-    uint32_t* parts = (uint32_t*)(bits + align256(nkeys * per_key));
-    if (sliced)
-        HIP_TRY(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes,
-                                                  (uint32_t)nkeys, (uint32_t*)d_ans, parts, st));
-    else
-        HIP_TRY(dpfk::launch_pir_fold((const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes, (uint32_t)nkeys,
-                                      (uint32_t*)d_ans, parts, st));
+    HIP_TRY((sliced ? dpfk::launch_pir_fold_sliced : dpfk::launch_pir_fold)(
+        (const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes, (uint32_t)nkeys, (uint32_t*)d_ans, parts, st));
     return DPF_OK;
 }
 
-int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
-                                   uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
-                                   size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
-    if (rec_bytes == 32)
-        return dpf_pir_answer_sliced_dev(device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, d_ans, d_work,
-                                         stream);
-    return pir_answer_wide(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, rec_bytes, d_ans,
-                           d_work, stream);
+int dpf_pir_answer_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                       uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, uint8_t* d_ans,
+                       void* d_work, void* stream) {
+    return pir_answer(false, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, 32, d_ans, d_work, stream);
+}
+
+int dpf_pir_answer_sliced_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                              uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                              uint8_t* d_ans, void* d_work, void* stream) {
+    return pir_answer(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, 32, d_ans, d_work, stream);
 }
 
 int dpf_pir_answer_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
                             uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
                             uint8_t* d_ans, void* d_work, void* stream) {
-    if (rec_bytes == 32)
-        return dpf_pir_answer_dev(device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, d_ans, d_work, stream);
-    return pir_answer_wide(false, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, rec_bytes, d_ans,
-                           d_work, stream);
+    return pir_answer(false, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_db, nrec, rec_bytes, d_ans, d_work,
+                      stream);
+}
+
+int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                                   uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                                   size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
+    return pir_answer(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, rec_bytes, d_ans, d_work,
+                      stream);
+}
+
+int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_dbs,
+                            uint64_t nrec, uint8_t* d_ans, void* d_work, void* stream) {
+    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
+    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
+    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
+        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    if (nkeys == 0) return DPF_OK;
+    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, 32, (uint32_t)nkeys,
+                                         (uint32_t*)d_ans, (uint32_t*)d_work, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+// ---- records of rec_bytes = 32 C bytes over the sliced layout -------------
+size_t dpf_pir_db_sliced_size_wide(uint64_t nrec, size_t rec_bytes) {
+    if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES) return 0;
+    return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec, rec_bytes));
+}
+
+int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                              void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_slice_db(d_db, nrec, rec_bytes, d_dbs, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                 void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (rec_bytes == 32) return dpf_xor_fold_sliced_dev(device, d_bits, bits_stride, nkeys, d_dbs, nrec, d_ans, d_work, stream);
+    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
+    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
+    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0 || (uintptr_t)d_work % 16 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
+        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    if (nkeys == 0) return DPF_OK;
+    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, rec_bytes,
+                                         (uint32_t)nkeys, (uint32_t*)d_ans, (uint32_t*)d_work, (hipStream_t)stream));
+    return DPF_OK;
 }
 
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
@@ -1380,8 +1322,8 @@ int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, u
         for (uint64_t r0 = lo; ok && r0 < hi; r0 += chunk) {
             const uint64_t n = std::min<uint64_t>(chunk, hi - r0);
             ok = hipMemcpy(tmp, db + r0 * rec_bytes, n * rec_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-                 dpfk::launch_slice_db_wide((const uint8_t*)tmp, n, rec_bytes, (uint8_t*)p + (r0 - lo) * rec_bytes,
-                                            nullptr) == hipSuccess &&
+                 dpfk::launch_slice_db((const uint8_t*)tmp, n, rec_bytes, (uint8_t*)p + (r0 - lo) * rec_bytes,
+                                       nullptr) == hipSuccess &&
                  hipDeviceSynchronize() == hipSuccess;   // tmp is reused by the next chunk
         }
         (void)hipFree(tmp);

@@ -153,11 +153,8 @@ __device__ __forceinline__ uint2 valid_mask(uint64_t cc, uint64_t nrec, bool liv
 #ifndef DPF_FZ_TOUCH
 #define DPF_FZ_TOUCH 1        // k_pir_fused producers touch the next super-group into L2
 #endif
-#ifndef DPF_FOLD_ABLATE
-#define DPF_FOLD_ABLATE 0   // measurement builds of k_fold_mfma: 1 = loads only, 2 = no HBM reads (wrong answers)
-#endif
 // A streamed 16-byte operand; NT: a nontemporal load (the `nt` cache policy),
-// for DB slices too large to stay in the caches between batches (launch_mfma_mt).
+// for DB slices too large to stay in the caches between batches (launch_mfma).
 typedef uint32_t fold_nt4 __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ uint4 fold_ld(const uint4* p) {
@@ -168,9 +165,6 @@ __device__ __forceinline__ uint4 fold_ld(const uint4* p) {
         return *p;
     }
 }
-#ifndef DPF_FOLD_GLDS_DEFAULT
-#define DPF_FOLD_GLDS_DEFAULT 0   // launch_mfma_mt: LDS-DMA fold shape (fold_glds_mode)
-#endif
 #ifndef DPF_FOLD_PRIO
 #define DPF_FOLD_PRIO 1   // issue priority by progress (fold_prio)
 #endif
@@ -714,7 +708,7 @@ hipError_t fold_pass(const FoldArgs& a, bool direct, int kw, uint32_t* ans, uint
 // is a {0,1} product of [keys x records] by [records x 256 bit positions], so
 // it runs on v_mfma_scale_f32_32x32x64_f8f6f4 with e2m1 (FP4) operands: every
 // product is exactly 1 or 0, the fp32 accumulators hold exact counts (far
-// below 2^24 per wave), and the parity is the answer bit.  No LDS at all.
+// below 2^24 per workgroup, see below), and the parity is the answer bit.
 //
 // Operands.  An MFMA operand lane holds 32 K-values (records) of ONE row
 // (key) or column (bit position); the K order inside the lane is ours to
@@ -722,12 +716,15 @@ hipError_t fold_pass(const FoldArgs& a, bool direct, int kw, uint32_t* ans, uint
 // selection word = 32 consecutive records of one key.  The DB side needs the
 // transposed form -- for bit position n, one word of 32 consecutive records
 // -- which the PIR server builds once when the DB is loaded (the "sliced"
-// layout, k_slice_db below):
-//   dbs[S][n][g] (u32), S = super-group of 256 records, n < 256 bit position,
-//   g < 8 record group; bit j = bit n of record 256 S + 32 g + j.
-// A lane (n, h) loads dbs[S][n][4h .. 4h+3] and a key lane (k, h) loads
-// selection words 8S + 4h .. +3 (one dwordx4 each, both coalesced): K-block
-// t < 4 of super-group S is record groups t (h = 0) and 4 + t (h = 1).
+// layout, k_slice_db below).  A record of rec_bytes = 32 C bytes is C 32-byte
+// columns:
+//   dbs[S][c][n][g] (u32), S = super-group of 256 records, c < C column,
+//   n < 256 bit position of the column, g < 8 record group; bit j = bit n of
+//   bytes [32c, 32c + 32) of record 256 S + 32 g + j
+// (32-byte records: C = 1, dbs[S][n][g]).  A lane (n, h) loads
+// dbs[S][c][n][4h .. 4h+3] and a key lane (k, h) takes selection words
+// 8S + 4h .. +3 (one dwordx4 each): K-block t < 4 of super-group S is record
+// groups t (h = 0) and 4 + t (h = 1).
 // Word -> FP4 operand in registers, nibble i of dword d = record 4i + d:
 //   one side  d0 = x & 0x1..  (0.5)  d1 = x & 0x2.. (1.0)  d2 = x & 0x4.. (2.0)
 //             d3 = (x >> 1) & 0x4.. (2.0)                       5 VALU per word
@@ -736,11 +733,44 @@ hipError_t fold_pass(const FoldArgs& a, bool direct, int kw, uint32_t* ans, uint
 // so every nonzero product is exactly 1 with unit (E8M0 127) scales.
 //
 // Mapping.  A wave covers MT key tiles (32 keys) x NT bit tiles (32 bit
-// positions) of a contiguous run of super-groups; the 8/NT waves of a
-// workgroup split the record's 256 bits and share its selection words (L1).
-// At the end each accumulator register's parities become two answer words by
-// one ballot (C/D layout: lane = column n, register e = rows (e&3) +
-// 8(e>>2) + 4h), written to the workgroup's partial; k_xor_parts combines.
+// positions) of one column over a contiguous run of super-groups.  To the
+// fold a wide record is a record of 8 C bit tiles instead of 8, and a
+// selection operand is the same for every tile, so a workgroup takes a column
+// group of CG columns: CG * NS waves, NS = 8 / NT; wave wv folds bit slice
+// wv % NS of column wv / NS of the group.  Then
+//   - a staged block's selection rows are loaded and written to LDS once for
+//     all CG columns (selection bytes per DB byte 1 / (4 CG));
+//   - the workgroup's DB stream is runs of CG * 8 KiB, one per super-group.
+// Column groups are the grid's y dimension: every workgroup of a launch holds
+// a (super-group run, column group) pair, workgroups per launch x * y <= the
+// workgroup cap.  At the end each accumulator register's parities become two
+// answer words by one ballot (C/D layout: lane = column n, register e = rows
+// (e&3) + 8(e>>2) + 4h), written to the workgroup's partial, and one
+// k_xor_parts launch combines
+//   parts[x][key][8 CG y words]
+// into the answers.  32-byte records are ncols = 1, CG = 1, grid.y = 1.  CG is
+// the largest of 4, 2, 1 that divides C, capped by what the tile shape's
+// registers allow (launch_pir_fold_sliced).
+//
+// Selection words reach the waves through LDS: per block of SG super-groups
+// the workgroup copies each key's SG*32-byte span (coalesced) into a padded
+// row, and the next block's selection words and DB pieces are in flight in
+// registers while this block is folded (block-level double buffering: a
+// super-group of MFMA work is ~0.2-0.4 us per wave, shorter than the HBM
+// latency under load).  Loaded straight into the operand lanes, 16 B per
+// lane from 32 rows 2 MiB apart, the fold fetched ~1.6x its bytes and ran at
+// a third of the HBM rate (profiles/r04/fold_v1).
+//
+// Exactness of the fp32 counts: an accumulator gains at most 64 per MFMA
+// (one per record of a K-block), and fp32 holds every integer up to 2^24.
+// A workgroup's run of super-groups would grow with the DB and shrink with
+// the CU count, so launch_mfma never gives one more than
+// kFoldMaxSgPerBlock = 2^15 super-groups (2^23 records): it adds workgroups,
+// and beyond kFoldMaxBlocks of them it folds the DB in passes, each pass's
+// partials XORed into the answers.  (Reducing the counts to parities inside
+// the kernel moved the large-tile accumulators out of AGPRs and spilled them:
+// 2.5x slower at 256 keys, r05.)  wlim: selection words per key row from
+// `bits` (the row stride stays wpk), so a pass can start mid-row.
 typedef int fold_v8i __attribute__((ext_vector_type(8)));
 typedef float fold_v16f __attribute__((ext_vector_type(16)));
 
@@ -748,10 +778,8 @@ typedef float fold_v16f __attribute__((ext_vector_type(16)));
 // 1, 2, 2) and which the 7-op one (weights 2, 1, 0.5, 0.5): a selection
 // operand feeds NT MFMAs and a DB operand MT, so per MFMA the VALU cost is
 // sel/NT + db/MT, lowest with the cheap form on the side with fewer tiles
-// (kernel template below; DPF_FOLD_SEL_CHEAP=0/1 forces one for A/B runs).
-#ifndef DPF_FOLD_SEL_CHEAP
-#define DPF_FOLD_SEL_CHEAP -1
-#endif
+// (SC = NT < MT in the kernel: the selection side for the 4- and 8-key-tile
+// shapes, the DB side for the others).
 __device__ __forceinline__ fold_v8i fp4_w5(uint32_t x) {     // weights 0.5, 1, 2, 2
     fold_v8i r;
     r[0] = (int)(x & 0x11111111u);
@@ -779,764 +807,18 @@ __device__ __forceinline__ uint32_t u4w(const uint4& v, int t) { return t == 0 ?
 constexpr int kFoldFp4 = 4;         // cbsz / blgp format code of e2m1
 constexpr int kE8M0One = 127;       // block scale 2^0
 
-// Selection words reach the waves through LDS: per block of SG super-groups
-// the workgroup copies each key's SG*32-byte span (coalesced) into a padded
-// row, and the next block's selection words and DB pieces are in flight in
-// registers while this block is folded (block-level double buffering: a
-// super-group of MFMA work is ~0.2-0.4 us per wave, shorter than the HBM
-// latency under load).  Loaded straight into the operand lanes, 16 B per
-// lane from 32 rows 2 MiB apart, the fold fetched ~1.6x its bytes and ran at
-// a third of the HBM rate (profiles/r04/fold_v1).
-#ifndef DPF_FOLD_PD
-#define DPF_FOLD_PD 1   // staged blocks in flight ahead of the one being folded (1 or 2)
-#endif
-// KG key groups per workgroup: wave w takes bit slice w % (8/NT) of key
-// group w / (8/NT), so a workgroup covers 32*MT*KG keys x 256 bits.
-// SGM: the selection bits are super-group-major in chunks of G super-groups,
-// sel[S / G][sgm_keys][G * 8 words] (G = sgm_g: 1, or 4 = one 128-byte line
-// of a key per chunk, as the PIR tree kernel writes them), so a staged block
-// is one contiguous region instead of EvalFull's key-major [key][wpk words].
-// Exactness of the fp32 counts: an accumulator gains at most 64 per MFMA
-// (one per record of a K-block), and fp32 holds every integer up to 2^24.
-// A workgroup's run of super-groups would grow with the DB and shrink with
-// the CU count, so launch_mfma_mt never gives one more than
-// kFoldMaxSgPerBlock = 2^15 super-groups (2^23 records): it adds workgroups,
-// and beyond kFoldMaxBlocks of them it folds the DB in passes, each pass's
-// partials XORed into the answers.  (Reducing the counts to parities inside
-// the kernel moved the large-tile accumulators out of AGPRs and spilled them:
-// 2.5x slower at 256 keys, r05.)  wlim: selection words per key row from
-// `bits` (the row stride stays wpk), so a pass can start mid-row.
-#ifndef DPF_FOLD_MINB4
-#define DPF_FOLD_MINB4 2   // min workgroups per CU the <=4-tile shapes are compiled for (A/B: 4 = <=128 VGPRs)
-#endif
-template <int MT, int NT, int SG, int KG, int SGM = 0, bool NTDB = false>
-__global__ __launch_bounds__(64 * (8 / NT) * KG, (MT * NT <= 4) ? DPF_FOLD_MINB4 : 1) void k_fold_mfma(
-    const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
-    uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
-    uint64_t wlim, uint32_t sgm_keys = 0) {
-    constexpr int NS = 8 / NT;                                 // bit slices
-    constexpr int NW = NS * KG;
-    constexpr bool SC = DPF_FOLD_SEL_CHEAP >= 0 ? DPF_FOLD_SEL_CHEAP == 1 : NT < MT;
-    constexpr int kRows = 32 * MT * KG;
-    constexpr int kRow = SG * 8 + 4;                           // words per staged row (+4: conflict-free b128 reads)
-    constexpr int kPieces = kRows * (SG * 2);                  // uint4 pieces per staged block
-    constexpr int kPer = (kPieces + 64 * NW - 1) / (64 * NW);  // per thread
-    __shared__ __attribute__((aligned(16))) uint32_t s_sel[kRows * kRow];
-    zero_answers(zero, zero_words);
-    const uint32_t l = threadIdx.x & 63, h = l >> 5, r = l & 31;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t w = wv % NS, kg = wv / NS;                   // bit slice, key group
-    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
-    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
-    if (s0 >= s1) return;                                       // uniform over the workgroup
-    // Staging role: piece p = threadIdx.x + i*64*NW is row p/(2SG), 16 bytes p%(2SG).
-    // Piece p -> (row, q = 16-byte piece of the row's block span): key-major,
-    // row = p / 2SG; super-group-major, p = (s * kRows + row) * 2 + half.
-    auto piece = [&](uint32_t p, uint32_t& row, uint32_t& q) __attribute__((always_inline)) {
-        if constexpr (SGM == 1) {
-            row = (p >> 1) % kRows;
-            q = 2 * ((p >> 1) / kRows) + (p & 1);
-        } else {
-            row = p / (2 * SG);
-            q = p % (2 * SG);
-        }
-    };
-    auto load_sel = [&](uint64_t sb, uint4 (&v)[kPer]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < kPer; ++i) {
-            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
-            uint32_t row, q;
-            piece(p, row, q);
-            const uint64_t word = sb * 8 + 4 * q;
-            const bool ok = p < (uint32_t)kPieces && row < nkeys && word + 4 <= wlim;
-            const uint64_t S = sb + q / 2;
-            const uint64_t at = SGM ? ((S / SGM * sgm_keys + row) * SGM + S % SGM) * 8 + 4 * (q & 1)
-                                    : (uint64_t)row * wpk + word;
-#if DPF_FOLD_ABLATE == 2
-            const uint32_t z = (uint32_t)at * 2654435761u;      // no HBM read (measurement build)
-            const uint4 x = make_uint4(z, z ^ 0x5555u, z + 7u, ~z);
-#else
-            const uint4 x = *reinterpret_cast<const uint4*>(bits + (ok ? at : 0));
-#endif
-            v[i] = ok ? x : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto store_sel = [&](const uint4 (&v)[kPer]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < kPer; ++i) {
-            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
-            uint32_t row, q;
-            piece(p, row, q);
-            if (p < (uint32_t)kPieces) *reinterpret_cast<uint4*>(&s_sel[row * kRow + 4 * q]) = v[i];
-        }
-    };
-    // DB pieces of a whole block (clamped past the range; never folded).
-    auto load_db = [&](uint64_t sb, uint4 (&B)[SG][NT]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl) {
-            const uint64_t S = sb + sl < s1 ? sb + sl : s1 - 1;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-#if DPF_FOLD_ABLATE == 2
-                const uint32_t z = (uint32_t)((S * 256 + 32u * (w * NT + j) + r) * 2 + h) * 2246822519u;
-                B[sl][j] = make_uint4(z, z + 1u, z ^ 0xAAAAu, ~z);           // no HBM read (measurement build)
-#else
-                B[sl][j] = fold_ld<NTDB>(&dbs[(S * 256 + 32u * (w * NT + j) + r) * 2 + h]);
-#endif
-            }
-        }
-    };
-    fold_v16f acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.0f;
-    // One super-group: 4 K-blocks of 64 records x MT x NT MFMAs.
-    auto fold_sg = [&](int sl, const uint4 (&B)[NT]) __attribute__((always_inline)) {
-        uint4 A[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-            A[m] = *reinterpret_cast<const uint4*>(&s_sel[(32 * (MT * kg + m) + r) * kRow + 8 * sl + 4 * h]);
-#if DPF_FOLD_ABLATE == 1
-        // Measurement build: the operands are consumed by one XOR each, no
-        // FP4 expansion and no MFMA (the load + staging structure alone).
-        uint32_t x = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) x ^= u4w(B[j], t);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) x ^= u4w(A[m], t);
-        }
-        acc[0][0][0] += (float)(x & 1u);
-#else
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            fold_v8i bo[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bo[j] = fp4_db<SC>(u4w(B[j], t));
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const fold_v8i ao = fp4_sel<SC>(u4w(A[m], t));
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[m][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bo[j], acc[m][j], kFoldFp4, kFoldFp4,
-                                                                               0, kE8M0One, 0, kE8M0One);
-            }
-        }
-#endif
-    };
-#if DPF_FOLD_PD >= 2
-    // Two blocks in flight: block i folds from buffer i%3 while blocks i+1
-    // and i+2 load (selection words and DB pieces rotate over 3 sets).
-    uint4 sv0[kPer], sv1[kPer], sv2[kPer];
-    uint4 B0[SG][NT], B1[SG][NT], B2[SG][NT];
-    load_sel(s0, sv0);
-    load_db(s0, B0);
-    load_sel(s0 + SG < s1 ? s0 + SG : s0, sv1);
-    load_db(s0 + SG < s1 ? s0 + SG : s0, B1);
-    auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bf)[SG][NT], const uint4 (&svc)[kPer],
-                     uint4 (&svf)[kPer]) __attribute__((always_inline)) {
-        fold_prio(sb - s0, s1 - s0);
-        lds_barrier();                                          // previous block's operand reads are done
-        store_sel(svc);
-        lds_barrier();
-        const uint64_t nb = sb + 2 * SG < s1 ? sb + 2 * SG : sb;   // block after next (clamped)
-        load_sel(nb, svf);
-        load_db(nb, Bf);
-        const uint64_t n = s1 - sb;
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl)
-            if ((uint64_t)sl < n) fold_sg(sl, Bc[sl]);
-    };
-    uint64_t sb = s0;
-    for (; sb + 2 * SG < s1; sb += 3 * SG) {
-        block(sb, B0, B2, sv0, sv2);
-        block(sb + SG, B1, B0, sv1, sv0);
-        block(sb + 2 * SG, B2, B1, sv2, sv1);
-    }
-    if (sb < s1) block(sb, B0, B2, sv0, sv2);
-    if (sb + SG < s1) block(sb + SG, B1, B0, sv1, sv0);
-#else
-    uint4 sv[kPer];
-    uint4 BA[SG][NT], BB[SG][NT];
-    load_sel(s0, sv);
-    load_db(s0, BA);
-    // One staged block: its selection rows to LDS, the next block's loads
-    // issued, then its super-groups folded.
-    auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bn)[SG][NT]) __attribute__((always_inline)) {
-        fold_prio(sb - s0, s1 - s0);
-        lds_barrier();                                          // previous block's operand reads are done
-        store_sel(sv);
-        lds_barrier();
-        const uint64_t nb = sb + SG < s1 ? sb + SG : sb;        // next block (clamped)
-        load_sel(nb, sv);
-        load_db(nb, Bn);
-        const uint64_t n = s1 - sb;
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl)
-            if ((uint64_t)sl < n) fold_sg(sl, Bc[sl]);
-    };
-    uint64_t sb = s0;
-    for (; sb + SG < s1; sb += 2 * SG) {
-        block(sb, BA, BB);
-        block(sb + SG, BB, BA);
-    }
-    if (sb < s1) block(sb, BA, BB);
-#endif
-    // Parities -> answer words: parts[block][key][8] (word = bit tile).
-    constexpr uint32_t pkeys = 32 * MT * KG;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            uint32_t out = 0;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t p = ((uint32_t)acc[m][j][e]) & 1u;
-                const uint64_t b = __builtin_amdgcn_ballot_w64(p != 0);
-                const uint32_t row0 = (e & 3) + 8 * (e >> 2);
-                out = l == row0 ? (uint32_t)b : out;
-                out = l == row0 + 4 ? (uint32_t)(b >> 32) : out;
-            }
-            if (l < 32) parts[((uint64_t)blockIdx.x * pkeys + 32 * (MT * kg + m) + l) * 8 + w * NT + j] = out;
-        }
-}
-
-#ifndef DPF_FOLD_GLDS_KERNEL
-#define DPF_FOLD_GLDS_KERNEL 0   // k_fold_glds: experimental build only (measured slower, r05)
-#endif
-#if DPF_FOLD_GLDS_KERNEL
-// ---------------------------------------------------------------------------
-// k_fold_glds: k_fold_mfma with its operands staged by LDS-DMA (r05).
-// PMC on k_fold_mfma<2,2,2,1> at configs[4] (profiles/r05/pmc_fold64): MFMA
-// busy 43% of cycles, TA busy 61-69%, HBM 5.2 TB/s (0.84 of the measured
-// streaming rate), waves waiting on memory 46% of their cycles, 3 waves per
-// SIMD: no unit is saturated; the fold is bound by the bytes it keeps in
-// flight (one staged block of ~20 KiB per workgroup in VGPRs, ~60 KiB per CU
-// against the ~60 KiB that Little's law asks at 6 TB/s and ~2.5 us of loaded
-// latency).  Here global_load_lds_dwordx4 moves every operand straight into
-// a P-deep ring in LDS (no VGPR cost), so P - 1 blocks stay in flight while
-// one is folded; a raw s_barrier plus a counted vmcnt wait per block (never
-// vmcnt(0) in the loop) keeps them in flight across the barrier.
-//   stage = selection rows [kRows][2 SG x 16 B] (XOR-swizzled pieces:
-//           conflict-free ds_read_b128 of a key tile) + each wave's DB
-//           pieces [SG][NT][64 lanes x 16 B];
-//   every wave issues G = 1 + SG * NT LDS-DMAs per block (its share of the
-//   selection rows, then its own DB pieces), so one vmcnt count fits all.
-// Blocks past the end are issued with clamped addresses into the stage that
-// will not be read again, so the count holds to the last block.
-// Only the key-major selection layout (sgm_keys == 0).
-template <int MT, int NT, int SG, int KG, int P>
-struct GldsShape {
-    static constexpr int NS = 8 / NT, NW = NS * KG;
-    static constexpr int kRows = 32 * MT * KG;
-    static constexpr int PR = 2 * SG;                        // 16-byte pieces per selection row
-    static constexpr int kSelPieces = kRows * PR;
-    static constexpr int kSelLanes = kSelPieces / NW;        // per wave (one LDS-DMA, <= 64 lanes)
-    static constexpr int kDbPieces = NW * SG * NT * 64;
-    static constexpr int kStage = kSelPieces + kDbPieces;    // 16-byte slots per stage
-    static constexpr int G = 1 + SG * NT;                    // LDS-DMAs per wave per block
-    static_assert(kSelPieces % NW == 0 && kSelLanes <= 64, "selection rows: one DMA per wave");
-    static_assert(16 % PR == 0, "swizzle: pieces per row divide a bank row");
-};
-template <int PR>
-__device__ __forceinline__ uint32_t sel_slot(uint32_t row, uint32_t q) {
-    constexpr uint32_t rpb = 16 / PR;                        // rows per 256-byte bank row
-    return row * PR + (q ^ ((row / rpb) & (PR - 1)));
-}
-// The gfx950-only builtins sit behind the device pass: in the host pass
-// clang treats them as invalid in the kernel template's body and silently
-// drops the kernel's host stub (undefined symbol at link time).
-template <int N>
-__device__ __forceinline__ void wait_vm() {                  // s_waitcnt vmcnt(N), nothing else
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-#endif
-}
-__device__ __forceinline__ void wait_lgkm0() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_s_waitcnt((15) | (3 << 14) | (7 << 4) | (0 << 8));
-#endif
-}
-// ds_read_b128 hidden from the compiler: an ordinary LDS read of the ring
-// makes hipcc wait vmcnt(0) for every LDS-DMA in flight (it cannot tell the
-// stages apart), which drains the pipeline each block.  The caller passes
-// the results through lgkm_ready() before using them: the compiler sees no
-// dependence between the asm load and a plain s_waitcnt, and would hoist
-// the uses above the wait.
-typedef uint32_t fold_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ fold_u4 lds_read16(const uint4* p) {
-    fold_u4 v;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint4*)p;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a));
-#else
-    v = fold_u4{p->x, p->y, p->z, p->w};
-#endif
-    return v;
-}
-// s_waitcnt lgkmcnt(0) tied to v: uses of v stay below the wait.
-__device__ __forceinline__ void lgkm_ready(fold_u4& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v));
-#else
-    (void)v;
-#endif
-}
-// global_load_lds_dwordx4: 16 bytes per lane from g to LDS at l + 16 * lane
-// (l wave-uniform).
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-#else
-    (void)g;
-    (void)l;
-#endif
-}
-
-template <int MT, int NT, int SG, int KG, int P>
-__global__ __launch_bounds__(64 * (8 / NT) * KG, 2) void k_fold_glds(
-    const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
-    uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
-    uint64_t wlim) {
-    using Sh = GldsShape<MT, NT, SG, KG, P>;
-    constexpr int NS = Sh::NS, PR = Sh::PR;
-    constexpr bool SC = DPF_FOLD_SEL_CHEAP >= 0 ? DPF_FOLD_SEL_CHEAP == 1 : NT < MT;
-    __shared__ __attribute__((aligned(16))) uint4 s_ring[P * Sh::kStage];   // the only LDS object (glds waits)
-    zero_answers(zero, zero_words);
-    const uint32_t l = threadIdx.x & 63, h = l >> 5, r = l & 31;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t w = wv % NS, kg = wv / NS;
-    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
-    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
-    if (s0 >= s1) return;                                    // uniform over the workgroup
-    const uint64_t nblk = (s1 - s0 + SG - 1) / SG;
-    // Issue block b into stage b % P (clamped past the end).
-    auto issue = [&](uint64_t b) __attribute__((always_inline)) {
-        uint4* st = s_ring + (uint32_t)(b % P) * Sh::kStage;
-        const uint64_t sb = s0 + (b < nblk ? b : nblk - 1) * SG;
-        // selection rows: this wave's kSelLanes slots
-        if (l < (uint32_t)Sh::kSelLanes) {
-            const uint32_t slot = wv * Sh::kSelLanes + l;
-            const uint32_t row = slot / PR, qs = slot % PR;
-            const uint32_t q = qs ^ ((row / (16 / PR)) & (PR - 1));
-            const uint32_t krow = row < nkeys ? row : nkeys - 1;
-            uint64_t word = sb * 8 + 4 * q;
-            if (word + 4 > wlim) word = wlim - 4;
-            glds16(bits + (uint64_t)krow * wpk + word, st + wv * Sh::kSelLanes);
-        }
-        // this wave's DB pieces
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl) {
-            const uint64_t S = sb + sl < s1 ? sb + sl : s1 - 1;
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                glds16(dbs + (S * 256 + 32u * (w * NT + j) + r) * 2 + h,
-                       st + Sh::kSelPieces + ((wv * SG + sl) * NT + j) * 64);
-        }
-    };
-    fold_v16f acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.0f;
-#pragma unroll
-    for (int b = 0; b < P - 1; ++b) issue((uint64_t)b);
-    for (uint64_t b = 0; b < nblk; ++b) {
-        fold_prio(b, nblk);
-        wait_vm<Sh::G * (P - 2)>();                          // this wave's DMAs of block b have landed
-        wait_lgkm0();
-        __builtin_amdgcn_s_barrier();                        // ... and every wave's; block b - 1 fully read
-        issue(b + P - 1);                                    // into the stage block b - 1 used
-        const uint4* st = s_ring + (uint32_t)(b % P) * Sh::kStage;
-        const uint64_t n = s1 - (s0 + b * SG);
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl) {
-            if ((uint64_t)sl >= n) break;
-            fold_u4 A[MT], B[NT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m) A[m] = lds_read16(st + sel_slot<PR>(32 * (MT * kg + m) + r, 2 * sl + h));
-#pragma unroll
-            for (int j = 0; j < NT; ++j) B[j] = lds_read16(st + Sh::kSelPieces + ((wv * SG + sl) * NT + j) * 64 + l);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) lgkm_ready(A[m]);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) lgkm_ready(B[j]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                fold_v8i bo[NT];
-#pragma unroll
-                for (int j = 0; j < NT; ++j) bo[j] = fp4_db<SC>(B[j][t]);
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const fold_v8i ao = fp4_sel<SC>(A[m][t]);
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[m][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bo[j], acc[m][j], kFoldFp4,
-                                                                                   kFoldFp4, 0, kE8M0One, 0, kE8M0One);
-                }
-            }
-        }
-    }
-    wait_vm<0>();                                            // the clamped tail DMAs, before the waves exit
-    constexpr uint32_t pkeys = 32 * MT * KG;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            uint32_t out = 0;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t p = ((uint32_t)acc[m][j][e]) & 1u;
-                const uint64_t b = __builtin_amdgcn_ballot_w64(p != 0);
-                const uint32_t row0 = (e & 3) + 8 * (e >> 2);
-                out = l == row0 ? (uint32_t)b : out;
-                out = l == row0 + 4 ? (uint32_t)(b >> 32) : out;
-            }
-            if (l < 32) parts[((uint64_t)blockIdx.x * pkeys + 32 * (MT * kg + m) + l) * 8 + w * NT + j] = out;
-        }
-}
-
-#endif  // DPF_FOLD_GLDS_KERNEL
-
-// The sliced layout (above) from a row-major DB of 32-byte records: one wave
-// per 64 records (record groups 2q', 2q'+1 of a super-group); lane l holds
-// record l's 8 words and one ballot per bit position transposes 32 x 32 bits.
-__global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, uint64_t nrec,
-                                                   uint32_t* __restrict__ dbs, uint64_t nwaves) {
-    const uint64_t q = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (q >= nwaves) return;
-    const uint32_t l = threadIdx.x & 63;
-    const uint64_t rec = q * 64 + l;
-    uint4 a = make_uint4(0, 0, 0, 0), b = a;
-    if (rec < nrec) {
-        a = db[2 * rec];
-        b = db[2 * rec + 1];
-    }
-    const uint32_t wd[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const uint64_t S = q >> 2;
-    const uint32_t g = 2 * (uint32_t)(q & 3) + (l >> 5);
-#pragma unroll
-    for (int wi = 0; wi < 8; ++wi) {
-        uint32_t out = 0;
-#pragma unroll
-        for (int bb = 0; bb < 32; ++bb) {
-            const uint64_t m = __builtin_amdgcn_ballot_w64(((wd[wi] >> bb) & 1u) != 0);
-            out = l == (uint32_t)bb ? (uint32_t)m : out;
-            out = l == (uint32_t)bb + 32 ? (uint32_t)(m >> 32) : out;
-        }
-        dbs[(S * 256 + 32 * wi + (l & 31)) * 8 + g] = out;
-    }
-}
-
-// Few keys over the sliced DB: no matrix product needed.  Thread n of a
-// 256-thread workgroup owns bit position n; per super-group it reads its 8
-// words dbs[S][n][0..7] (the workgroup: 8 KiB contiguous) and, for every key
-// k, XORs (selection word & DB word) into acc[k] -- one v_bitop3 per word and
-// key, the selection words wave-uniform (scalar loads).  The answer bit
-// (k, n) is the parity of popcount(acc[k]).  Used for one key (97 us at
-// configs[4] against the MFMA fold's 103): with 4 or 16 keys its per-key
-// scalar loads serialise (131 / 388 us against 104 / 107,
-// profiles/r04/fold_ab/).
-// (Nontemporal DB loads, as the matrix-core fold takes them above 256 MiB,
-// measured 95.2-95.8 against 93.9-94.4 us here at 2^24 records: not used.)
-template <int KB, bool NTDB = false>
-__global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __restrict__ bits, uint64_t wpk,
-                                                            const uint4* __restrict__ dbs, uint64_t nsg,
-                                                            uint32_t nkeys, uint64_t sg_per_block,
-                                                            uint32_t* __restrict__ parts, uint32_t* __restrict__ zero,
-                                                            uint64_t zero_words) {
-    zero_answers(zero, zero_words);
-    const uint32_t n = threadIdx.x, l = n & 63;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
-    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
-    uint32_t acc[KB];
-#pragma unroll
-    for (int k = 0; k < KB; ++k) acc[k] = 0;
-    auto fold = [&](uint64_t S, const uint4& a, const uint4& b) __attribute__((always_inline)) {
-        const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        const bool in = 8 * S + 8 <= wpk;                      // uniform
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-            if ((uint32_t)k >= nkeys || !in) continue;         // uniform
-            const uint32_t* sel = bits + (uint64_t)k * wpk + 8 * S;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) acc[k] = xam(acc[k], x[g], sel[g]);
-        }
-        if (!in) {                                             // the key rows end inside this super-group
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                if ((uint32_t)k >= nkeys) continue;
-                const uint32_t* sel = bits + (uint64_t)k * wpk;
-#pragma unroll
-                for (int g = 0; g < 8; ++g)
-                    if (8 * S + g < wpk) acc[k] = xam(acc[k], x[g], sel[8 * S + g]);
-            }
-        }
-    };
-    uint64_t S = s0;
-    for (; S + 1 < s1; S += 2) {
-        const uint4 a0 = fold_ld<NTDB>(&dbs[(S * 256 + n) * 2]), b0 = fold_ld<NTDB>(&dbs[(S * 256 + n) * 2 + 1]);
-        const uint4 a1 = fold_ld<NTDB>(&dbs[((S + 1) * 256 + n) * 2]);
-        const uint4 b1 = fold_ld<NTDB>(&dbs[((S + 1) * 256 + n) * 2 + 1]);
-        fold(S, a0, b0);
-        fold(S + 1, a1, b1);
-    }
-    if (S < s1) fold(S, fold_ld<NTDB>(&dbs[(S * 256 + n) * 2]), fold_ld<NTDB>(&dbs[(S * 256 + n) * 2 + 1]));
-    // parts[block][key][8]: wave w holds answer words 2w (lanes 0-31) and 2w+1.
-#pragma unroll
-    for (int k = 0; k < KB; ++k) {
-        const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc[k]) & 1) != 0);
-        if (l < 2) parts[((uint64_t)blockIdx.x * KB + k) * 8 + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
-    }
-}
-
-uint64_t pir_sliced_bytes(uint64_t nrec) { return (nrec + 255) / 256 * 256 * 32; }
-
-hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint8_t* dbs, hipStream_t st) {
-    const uint64_t nsg = (nrec + 255) / 256;
-    if (nsg == 0) return hipSuccess;
-    const uint64_t nwaves = nsg * 4;
-    hipLaunchKernelGGL(k_slice_db, dim3((uint32_t)((nwaves + 3) / 4)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4*>(db), nrec, reinterpret_cast<uint32_t*>(dbs), nwaves);
-    return hipGetLastError();
-}
-
-namespace {
-#if DPF_FOLD_GLDS_KERNEL
-template <int MT, int NT, int SG, int KG, int P>
-hipError_t launch_glds(const uint32_t* bits, uint64_t wpk, uint64_t wlim, const uint8_t* dbs, uint64_t nsg, uint32_t nk,
-                       uint32_t* parts, uint32_t* zero, uint64_t zero_words, uint64_t want, uint64_t& blocks,
-                       hipStream_t st) {
-    constexpr int NW = 8 / NT * KG;
-    uint64_t spb;
-    split_chunks(nsg, want, SG, blocks, spb);
-    hipLaunchKernelGGL((k_fold_glds<MT, NT, SG, KG, P>), dim3((uint32_t)blocks), dim3(64 * NW), 0, st, bits, wpk,
-                       reinterpret_cast<const uint4*>(dbs), nsg, nk, spb, parts, zero, zero_words, wlim);
-    return hipGetLastError();
-}
-
-// DPF_FOLD_GLDS (env; measurement): 0 = register-staged k_fold_mfma, else
-// the LDS-DMA ring k_fold_glds for 33-64 keys: 1 = SG 2, P 4; 2 = SG 2, P 3;
-// 3 = SG 1, P 5; 4 = SG 1, P 6.
-static int fold_glds_mode() {
-    static const int m = [] {
-        const char* e = getenv("DPF_FOLD_GLDS");
-        return e ? atoi(e) : DPF_FOLD_GLDS_DEFAULT;
-    }();
-    return m;
-}
-
-#endif
-
-// The DB pieces of a matrix-core fold over at least this many DB bytes are
-// loaded nontemporal.  r05 (tools/archive/r05_nt.sh, profiles/r05/fold_nt/, B = 64,
-// fold us, nontemporal vs default): 2^24 x 32 B (512 MiB, twice the chip's
-// last-level cache) 123-125 vs 135-138, and B = 16 95 vs 105-107; 2^23 66-69
-// vs 67-74; but 2^22 39-40 vs 35-36 and 2^21 (an N = 8 rank) 25.5 vs 24.7:
-// slices that stay cached between batches lose.  DPF_FOLD_NT_MIN overrides.
-constexpr uint64_t kFoldNtMinBytes = 256ull << 20;
-static uint64_t fold_nt_min_bytes() {
-    static const uint64_t v = [] {
-        const char* e = getenv("DPF_FOLD_NT_MIN");
-        return e && *e ? strtoull(e, nullptr, 0) : kFoldNtMinBytes;
-    }();
-    return v;
-}
-
-// One key group (<= 32 * MT * KG keys) over the sliced DB: passes of at most
-// (workgroup cap) x kFoldMaxSgPerBlock super-groups, each a fold launch whose
-// workgroups fold <= kFoldMaxSgPerBlock super-groups (fp32-exact counts, see
-// k_fold_mfma) and a k_xor_parts launch that XORs the partials into ans.
-template <int MT, int NT, int SG, int KG>
-hipError_t launch_mfma_mt(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t nk,
-                          uint32_t* parts, uint32_t* ans, uint32_t* zero, uint64_t zero_words, hipStream_t st,
-                          uint32_t sgm_keys = 0, uint32_t sgm_g = 1) {
-    constexpr int NW = 8 / NT * KG;
-    // Resident workgroups only (one round): each takes a contiguous run of
-    // whole staged blocks.  (A fixed 4 workgroups per CU left 1/4 - 3/4 of
-    // them for a second round at 3 or 1 resident per CU.)
-    static int per_cu = [] {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma<MT, NT, SG, KG>, 64 * NW, 0) != hipSuccess || n < 1)
-            n = 1;
-        return n;
-    }();
-    static const int env_pcu = [] {                           // A/B runs: this many per CU (<= occupancy)
-        const char* e = getenv("DPF_FOLD_PER_CU");
-        return e && atoi(e) > 0 ? atoi(e) : 0;
-    }();
-    const uint64_t cap = g_fold_blocks.load(std::memory_order_relaxed);
-    const uint64_t msg = (uint64_t)fold_max_sg() / SG * SG > 0 ? (uint64_t)fold_max_sg() / SG * SG : SG;
-    // (The super-group-major layouts are measurement-only: one pass.)
-    const uint64_t per_pass = sgm_keys ? nsg : cap * msg;
-    const bool ntdb = nsg * 256 * 32 >= fold_nt_min_bytes();
-    // Two workgroups per CU instead of the occupancy limit (3 at 33-64 keys)
-    // for cached DB slices and for the one-key-tile shape: fewer partials to
-    // combine and less per-workgroup overhead (r05, tools/archive/r05_fpercu.sh,
-    // profiles/r05/fold_blocks/, medians of 5: 2^21 x 32 B 22.6 vs 24.7 us,
-    // 2^22 34.8 vs 36.0, B = 16 at 2^24 91.9 vs 96.6, B = 32 96.3 vs 99.8;
-    // but B = 64 at 2^23 / 2^24 67.9 / 130.7 vs 67.0 / 125.9).  One per CU
-    // for 33-64 keys over a slice of <= 64 MiB (the PIR rank at N = 8): rank
-    // step 0.0741-0.0750 vs 0.0742-0.0759 ms, lower in 5 of 6 interleaved
-    // pairs; at N = 4 (128 MiB) the pairs split 3 / 3 and the fold alone was
-    // slower (37.6 vs 33.9 us), so it keeps 2 (tools/archive/r05_fpercu1.sh,
-    // profiles/r05/fold_blocks/per_cu1_*.txt).
-    const bool small_slice = nsg * 256 * 32 <= (64ull << 20);
-    uint64_t pcu = small_slice && MT == 2 ? 1 : (!ntdb || MT == 1) && per_cu > 2 ? 2 : (uint64_t)per_cu;
-    if (env_pcu > 0) pcu = (uint64_t)(env_pcu < per_cu ? env_pcu : per_cu);
-    if (pcu > (uint64_t)per_cu) pcu = (uint64_t)per_cu;
-    const uint64_t resident = (uint64_t)cu_count_fold() * pcu;
-    for (uint64_t S0 = 0; S0 < nsg; S0 += per_pass) {
-        const uint64_t n = nsg - S0 < per_pass ? nsg - S0 : per_pass;
-        // enough workgroups that none folds more than msg super-groups
-        uint64_t want = (n + msg - 1) / msg;
-        if (want < resident) want = resident;
-        if (want > cap) want = cap;
-        const uint32_t* b = bits + (sgm_keys ? S0 / (sgm_g ? sgm_g : 1) * sgm_keys * (sgm_g ? sgm_g : 1) * 8 : S0 * 8);
-        const uint64_t wlim = wpk > S0 * 8 ? wpk - S0 * 8 : 0;
-        const uint8_t* d = dbs + S0 * 256 * 32;
-        uint32_t* z = S0 == 0 ? zero : nullptr;
-        const uint64_t zw = S0 == 0 ? zero_words : 0;
-        uint64_t blocks = 0;
-        hipError_t e = hipErrorUnknown;
-        bool done = false;
-#if DPF_FOLD_GLDS_KERNEL
-        if constexpr (MT == 2 && NT == 2 && KG == 1) {
-            if (!sgm_keys) {
-                done = true;
-                switch (fold_glds_mode()) {
-                    case 1: e = launch_glds<2, 2, 2, 1, 4>(b, wpk, wlim, d, n, nk, parts, z, zw, want, blocks, st); break;
-                    case 2: e = launch_glds<2, 2, 2, 1, 3>(b, wpk, wlim, d, n, nk, parts, z, zw, want, blocks, st); break;
-                    case 3: e = launch_glds<2, 2, 1, 1, 5>(b, wpk, wlim, d, n, nk, parts, z, zw, want, blocks, st); break;
-                    case 4: e = launch_glds<2, 2, 1, 1, 6>(b, wpk, wlim, d, n, nk, parts, z, zw, want, blocks, st); break;
-                    default: done = false;
-                }
-            }
-        }
-#endif
-        if (!done) {
-            uint64_t spb;
-            split_chunks(n, want, SG, blocks, spb, cap);
-            if (spb > msg) return hipErrorInvalidValue;    // fp32-exact counts: never more than msg per workgroup
-            if (sgm_keys && sgm_g == 4)
-                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, KG, 4>), dim3((uint32_t)blocks), dim3(64 * NW), 0, st, b,
-                                   wpk, reinterpret_cast<const uint4*>(d), n, nk, spb, parts, z, zw, wlim, sgm_keys);
-            else if (sgm_keys)
-                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, KG, 1>), dim3((uint32_t)blocks), dim3(64 * NW), 0, st, b,
-                                   wpk, reinterpret_cast<const uint4*>(d), n, nk, spb, parts, z, zw, wlim, sgm_keys);
-            else if (ntdb)
-                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, KG, 0, true>), dim3((uint32_t)blocks), dim3(64 * NW), 0, st,
-                                   b, wpk, reinterpret_cast<const uint4*>(d), n, nk, spb, parts, z, zw, wlim);
-            else
-                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, KG>), dim3((uint32_t)blocks), dim3(64 * NW), 0, st, b, wpk,
-                                   reinterpret_cast<const uint4*>(d), n, nk, spb, parts, z, zw, wlim);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) return e;
-        if (hipError_t e2 = launch_xor_parts(parts, blocks, nk, 32u * MT * KG, 8u, ans, 8, 0u, st); e2 != hipSuccess)
-            return e2;
-    }
-    return hipSuccess;
-}
-}  // namespace
-
-// Tile shape per key count (32 keys per tile): MT key tiles x NT bit tiles
-// per wave, KG key groups per workgroup.  DPF_FOLD_SHAPE picks among
-// measured alternatives for 65-256 keys (A/B builds).
-#ifndef DPF_FOLD_SLICED_DIRECT
-#define DPF_FOLD_SLICED_DIRECT 1    // keys up to which the sliced fold uses k_fold_sliced_direct (0: MFMA always)
-#endif
-#ifndef DPF_FOLD_SHAPE
-#define DPF_FOLD_SHAPE 0
-#endif
-#ifndef DPF_FOLD_SHAPE64
-#define DPF_FOLD_SHAPE64 0   // 33-64 keys
-#endif
-hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
-                                  uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st, uint32_t sgm_keys,
-                                  uint32_t sgm_g) {
-    if (nkeys == 0) return hipSuccess;
-    if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * 32, st);
-    if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
-    const uint64_t nsg = (nrec + 255) / 256;
-    if (nkeys <= (uint32_t)DPF_FOLD_SLICED_DIRECT && !sgm_keys) {   // one key: popcount fold, no MFMA
-        uint64_t blocks, spb;
-        split_chunks(nsg, (uint64_t)cu_count_fold() * 8, 2, blocks, spb);
-        const uint32_t kb = 1;
-        hipLaunchKernelGGL(k_fold_sliced_direct<1>, dim3((uint32_t)blocks), dim3(256), 0, st, bits, words_per_key,
-                           reinterpret_cast<const uint4*>(dbs), nsg, nkeys, spb, parts, ans, (uint64_t)nkeys * 8);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        return launch_xor_parts(parts, blocks, nkeys, kb, 8u, ans, 8, 0u, st);
-    }
-    for (uint32_t k0 = 0; k0 < nkeys; k0 += 256) {
-        const uint32_t nk = nkeys - k0 < 256 ? nkeys - k0 : 256;
-        const uint32_t* b = bits + (sgm_keys ? (uint64_t)k0 * 8 * sgm_g : (uint64_t)k0 * words_per_key);
-        uint32_t* zero = k0 == 0 ? ans : nullptr;
-        const uint64_t zw = k0 == 0 ? (uint64_t)nkeys * 8 : 0;
-        uint32_t* a = ans + (uint64_t)k0 * 8;
-        hipError_t e;
-#define DPF_MT(MT_, NT_, SG_, KG_) \
-    launch_mfma_mt<MT_, NT_, SG_, KG_>(b, words_per_key, dbs, nsg, nk, parts, a, zero, zw, st, sgm_keys, sgm_g)
-        if (nk <= 32) e = DPF_MT(1, 2, 4, 1);
-        else if (nk <= 64) {
-            if (DPF_FOLD_SHAPE64 == 1) e = DPF_MT(2, 2, 4, 1);
-            else if (DPF_FOLD_SHAPE64 == 2) e = DPF_MT(1, 2, 4, 2);
-            else if (DPF_FOLD_SHAPE64 == 3) e = DPF_MT(2, 4, 2, 1);
-            else if (DPF_FOLD_SHAPE64 == 4) e = DPF_MT(2, 2, 1, 1);
-            else e = DPF_MT(2, 2, 2, 1);
-        } else if (nk <= 128) {
-            if (DPF_FOLD_SHAPE == 1) e = DPF_MT(2, 4, 2, 2);
-            else e = DPF_MT(4, 2, 4, 1);
-        } else {
-            if (DPF_FOLD_SHAPE == 1) e = DPF_MT(2, 4, 2, 4);
-            else if (DPF_FOLD_SHAPE == 2) e = DPF_MT(4, 4, 2, 2);
-            else if (DPF_FOLD_SHAPE == 3) e = DPF_MT(2, 8, 2, 4);
-            else e = DPF_MT(8, 2, 4, 1);
-        }
-#undef DPF_MT
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// ---------------------------------------------------------------------------
-// Records wider than 32 bytes on the matrix cores.  A record of rec_bytes =
-// 32 C bytes is C 32-byte columns, and the sliced layout gains a column index
-// between the super-group and the bit position:
-//   dbs[S][c][n][g] (u32), c < C; bit j = bit n of bytes [32c, 32c + 32) of
-//   record 256 S + 32 g + j
-// (C = 1 is the layout above, byte for byte).  To the fold a wide record is a
-// record of 8 C bit tiles instead of 8: tile T = 8c + n/32 of super-group S
-// starts at u32 (S * 8C + T) * 256, and a selection operand is the same for
-// every tile.  k_fold_mfma_w is k_fold_mfma with that one change of address:
-// a workgroup takes a column group of CG columns (CG * NS waves, NS = 8 / NT: wave wv
-// folds bit slice wv % NS of column wv / NS of the group), so
-//   - a staged block's selection rows are loaded and written to LDS once for
-//     all CG columns (selection bytes per DB byte 1 / (4 CG), from 1 / 4);
-//   - the workgroup's DB stream is runs of CG * 8 KiB, one per super-group.
-// Column groups are the grid's y dimension: every workgroup of a launch holds
-// a (super-group run, column group) pair, workgroups per launch x * y <= the
-// workgroup cap, and one k_xor_parts launch combines
-//   parts[x][key][8 CG y words]
-// into the answers.  CG is the largest of 4, 2, 1 that divides C, capped by
-// what the tile shape's registers allow (launch_pir_fold_sliced_wide).
-// WPE: the waves per SIMD the shape is compiled for (its register budget).
+// k_fold_mfma<MT, NT, SG, CG, NTDB, WPE>: tile shape, super-groups per staged
+// block, columns per workgroup, nontemporal DB loads, and the waves per SIMD
+// the shape is compiled for (its register budget).  cg0: first column group
+// of the launch.
 template <int MT, int NT, int SG, int CG, bool NTDB, int WPE>
-__global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma_w(
+__global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
     const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
     uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
     uint64_t wlim, uint32_t ncols, uint32_t cg0) {
     constexpr int NS = 8 / NT;                                 // bit slices of a column
     constexpr int NW = NS * CG;
-    constexpr bool SC = DPF_FOLD_SEL_CHEAP >= 0 ? DPF_FOLD_SEL_CHEAP == 1 : NT < MT;
+    constexpr bool SC = NT < MT;                               // the selection side takes the cheap expansion
     constexpr int kRows = 32 * MT;
     constexpr int kRow = SG * 8 + 4;                           // words per staged row (+4: conflict-free b128 reads)
     constexpr int kPieces = kRows * (SG * 2);                  // uint4 pieces per staged block
@@ -1610,8 +892,8 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma_w(
     uint4 BA[SG][NT], BB[SG][NT];
     load_sel(s0, sv);
     load_db(s0, BA);
-    // One staged block, as in k_fold_mfma: its selection rows to LDS, the
-    // next block's loads issued, then its super-groups folded.
+    // One staged block: its selection rows to LDS, the next block's loads
+    // issued, then its super-groups folded.
     auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bn)[SG][NT]) __attribute__((always_inline)) {
         fold_prio(sb - s0, s1 - s0);
         lds_barrier();                                          // previous block's operand reads are done
@@ -1652,11 +934,12 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma_w(
         }
 }
 
-// The wide sliced layout from a row-major DB of 32 C-byte records: k_slice_db
-// with a column index.  Workgroup b = (super-group S, column c) = (b / C,
-// b % C); its 4 waves take 64 records each.
-__global__ __launch_bounds__(256) void k_slice_db_w(const uint4* __restrict__ db, uint64_t nrec, uint32_t ncols,
-                                                     uint32_t* __restrict__ dbs) {
+// The sliced layout (above) from a row-major DB of 32 C-byte records.
+// Workgroup b = (super-group S, column c) = (b / C, b % C); its 4 waves take
+// 64 records each: lane l holds the column's 8 words of record l and one
+// ballot per bit position transposes 32 x 32 bits.
+__global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, uint64_t nrec, uint32_t ncols,
+                                                   uint32_t* __restrict__ dbs) {
     const uint64_t S = blockIdx.x / ncols;
     const uint32_t c = blockIdx.x % ncols;
     const uint32_t l = threadIdx.x & 63, wq = threadIdx.x >> 6;
@@ -1681,14 +964,22 @@ __global__ __launch_bounds__(256) void k_slice_db_w(const uint4* __restrict__ db
     }
 }
 
-// One key over the wide sliced DB: k_fold_sliced_direct<1> with a column
-// index.  Workgroup (x, y) folds super-group run x of column y; thread n owns
-// bit position n of that column.  parts[x][8 C words].
-__global__ __launch_bounds__(256) void k_fold_sliced_direct_w(const uint32_t* __restrict__ bits,
-                                                              const uint4* __restrict__ dbs, uint64_t nsg,
-                                                              uint64_t sg_per_block, uint32_t* __restrict__ parts,
-                                                              uint32_t* __restrict__ zero, uint64_t zero_words,
-                                                              uint64_t wlim, uint32_t ncols, uint32_t c0) {
+// One key over the sliced DB: no matrix product needed.  Workgroup (x, y)
+// folds super-group run x of column c0 + y; thread n of its 256 owns bit
+// position n of that column.  Per super-group it reads its 8 words
+// dbs[S][c][n][0..7] (the workgroup: 8 KiB contiguous) and XORs (selection
+// word & DB word) into acc -- one v_bitop3 per word, the selection words
+// wave-uniform (scalar loads).  The answer bit n is the parity of
+// popcount(acc).  parts[x][8 y words].  One key only (97 us at configs[4]
+// against the MFMA fold's 103): with 4 or 16 keys the per-key scalar loads
+// serialise (131 / 388 us against 104 / 107, profiles/r04/fold_ab/).
+// (Nontemporal DB loads, as the matrix-core fold takes them above 256 MiB,
+// measured 95.2-95.8 against 93.9-94.4 us here at 2^24 records: not used.)
+__global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __restrict__ bits,
+                                                            const uint4* __restrict__ dbs, uint64_t nsg,
+                                                            uint64_t sg_per_block, uint32_t* __restrict__ parts,
+                                                            uint32_t* __restrict__ zero, uint64_t zero_words,
+                                                            uint64_t wlim, uint32_t ncols, uint32_t c0) {
     zero_answers(blockIdx.y == 0 ? zero : nullptr, zero_words);
     const uint32_t n = threadIdx.x, l = n & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1721,18 +1012,17 @@ __global__ __launch_bounds__(256) void k_fold_sliced_direct_w(const uint32_t* __
         parts[(uint64_t)blockIdx.x * (8u * gridDim.y) + 8 * blockIdx.y + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
 }
 
-uint64_t pir_sliced_bytes_wide(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * 256 * rec_bytes; }
+uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * 256 * rec_bytes; }
 
-hipError_t launch_slice_db_wide(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st) {
+hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st) {
     if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > kFoldMaxRecBytes) return hipErrorInvalidValue;
-    if (rec_bytes == 32) return launch_slice_db(db, nrec, dbs, st);
     const uint64_t nsg = (nrec + 255) / 256, C = rec_bytes / 32;
     if (nsg == 0) return hipSuccess;
     // One workgroup per (super-group, column), in launches of at most 2^30.
     const uint64_t per = (1ull << 30) / C;
     for (uint64_t S0 = 0; S0 < nsg; S0 += per) {
         const uint64_t n = nsg - S0 < per ? nsg - S0 : per;
-        hipLaunchKernelGGL(k_slice_db_w, dim3((uint32_t)(n * C)), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_slice_db, dim3((uint32_t)(n * C)), dim3(256), 0, st,
                            reinterpret_cast<const uint4*>(db + S0 * 256 * rec_bytes), nrec - S0 * 256, (uint32_t)C,
                            reinterpret_cast<uint32_t*>(dbs + S0 * 256 * rec_bytes));
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -1741,27 +1031,72 @@ hipError_t launch_slice_db_wide(const uint8_t* db, uint64_t nrec, uint64_t rec_b
 }
 
 namespace {
-// One key group (<= 32 MT keys) over the wide sliced DB, as launch_mfma_mt:
-// launches of x * y <= cap workgroups (x super-group runs of <= msg
-// super-groups, y column groups), each followed by one k_xor_parts.
+// The DB pieces of a matrix-core fold over at least this many DB bytes are
+// loaded nontemporal.  r05 (tools/archive/r05_nt.sh, profiles/r05/fold_nt/, B = 64,
+// fold us, nontemporal vs default): 2^24 x 32 B (512 MiB, twice the chip's
+// last-level cache) 123-125 vs 135-138, and B = 16 95 vs 105-107; 2^23 66-69
+// vs 67-74; but 2^22 39-40 vs 35-36 and 2^21 (an N = 8 rank) 25.5 vs 24.7:
+// slices that stay cached between batches lose.  DPF_FOLD_NT_MIN overrides.
+constexpr uint64_t kFoldNtMinBytes = 256ull << 20;
+uint64_t fold_nt_min_bytes() {
+    static const uint64_t v = [] {
+        const char* e = getenv("DPF_FOLD_NT_MIN");
+        return e && *e ? strtoull(e, nullptr, 0) : kFoldNtMinBytes;
+    }();
+    return v;
+}
+
+// Workgroups per CU of a matrix-core fold launch: resident workgroups only
+// (one round), each a contiguous run of whole staged blocks.  (A fixed 4
+// workgroups per CU left 1/4 - 3/4 of them for a second round at 3 or 1
+// resident per CU.)  occ: the shape's occupancy limit; C > 1 launches that.
+// 32-byte records (C = 1): two workgroups per CU instead of the occupancy
+// limit (3 at 33-64 keys) for cached DB slices and for the one-key-tile
+// shape: fewer partials to combine and less per-workgroup overhead (r05,
+// tools/archive/r05_fpercu.sh, profiles/r05/fold_blocks/, medians of 5:
+// 2^21 x 32 B 22.6 vs 24.7 us, 2^22 34.8 vs 36.0, B = 16 at 2^24 91.9 vs
+// 96.6, B = 32 96.3 vs 99.8; but B = 64 at 2^23 / 2^24 67.9 / 130.7 vs
+// 67.0 / 125.9).  One per CU for 33-64 keys over a slice of <= 64 MiB (the
+// PIR rank at N = 8): rank step 0.0741-0.0750 vs 0.0742-0.0759 ms, lower in
+// 5 of 6 interleaved pairs; at N = 4 (128 MiB) the pairs split 3 / 3 and the
+// fold alone was slower (37.6 vs 33.9 us), so it keeps 2
+// (tools/archive/r05_fpercu1.sh, profiles/r05/fold_blocks/per_cu1_*.txt).
+// DPF_FOLD_PER_CU=<n> (A/B runs, C = 1): this many, at most occ.
+uint64_t fold_per_cu(uint32_t C, int MT, bool ntdb, uint64_t slice_bytes, int occ) {
+    if (C > 1) return (uint64_t)occ;
+    static const int env_pcu = [] {
+        const char* e = getenv("DPF_FOLD_PER_CU");
+        return e && atoi(e) > 0 ? atoi(e) : 0;
+    }();
+    if (env_pcu > 0) return (uint64_t)(env_pcu < occ ? env_pcu : occ);
+    if (slice_bytes <= (64ull << 20) && MT == 2) return 1;
+    return (!ntdb || MT == 1) && occ > 2 ? 2 : (uint64_t)occ;
+}
+
+// One key group (<= 32 MT keys) over the sliced DB of C columns: launches of
+// x * y <= cap workgroups (x super-group runs, y column groups), in passes of
+// at most x * msg super-groups; each workgroup folds <= msg super-groups
+// (fp32-exact counts, see k_fold_mfma) and each fold launch is followed by a
+// k_xor_parts launch that XORs its partials into ans.
 template <int MT, int NT, int SG, int CG, int WPE>
-hipError_t launch_mfma_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C, uint32_t nk,
-                         uint32_t* parts, uint32_t* ans, uint32_t* zero, uint64_t zero_words, hipStream_t st) {
+hipError_t launch_mfma(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C, uint32_t nk,
+                       uint32_t* parts, uint32_t* ans, uint32_t* zero, uint64_t zero_words, hipStream_t st) {
     constexpr int NW = 8 / NT * CG;
     static_assert(32 * MT * CG * 32 <= (int)kFoldPartBytes, "a workgroup's partial fits its 16 KiB");
-    static int per_cu = [] {
+    static int occ = [] {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma_w<MT, NT, SG, CG, false, WPE>, 64 * NW, 0) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma<MT, NT, SG, CG, false, WPE>, 64 * NW, 0) !=
                 hipSuccess || n < 1)
             n = 1;
         return n;
     }();
     const uint64_t cap = g_fold_blocks.load(std::memory_order_relaxed);
     const uint64_t msg = (uint64_t)fold_max_sg() / SG * SG > 0 ? (uint64_t)fold_max_sg() / SG * SG : SG;
-    const bool ntdb = nsg * 256 * 32 * C >= fold_nt_min_bytes();   // by DB bytes
+    const uint64_t db_bytes = nsg * 256 * 32 * C;
+    const bool ntdb = db_bytes >= fold_nt_min_bytes();
     const uint64_t ncg = C / CG;
     const uint64_t gy_max = ncg < cap ? ncg : cap;
-    const uint64_t resident = (uint64_t)cu_count_fold() * (uint64_t)per_cu;
+    const uint64_t resident = (uint64_t)cu_count_fold() * fold_per_cu(C, MT, ntdb, db_bytes, occ);
     for (uint64_t g0 = 0; g0 < ncg; g0 += gy_max) {
         const uint64_t gy = ncg - g0 < gy_max ? ncg - g0 : gy_max;
         const uint64_t xcap = cap / gy;                          // >= 1
@@ -1782,10 +1117,10 @@ hipError_t launch_mfma_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs,
             const uint64_t zw = first ? zero_words : 0;
             const dim3 grid((uint32_t)blocks, (uint32_t)gy);
             if (ntdb)
-                hipLaunchKernelGGL((k_fold_mfma_w<MT, NT, SG, CG, true, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
+                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, CG, true, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
                                    nk, spb, parts, z, zw, wlim, C, (uint32_t)g0);
             else
-                hipLaunchKernelGGL((k_fold_mfma_w<MT, NT, SG, CG, false, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
+                hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, CG, false, WPE>), grid, dim3(64 * NW), 0, st, b, wpk, d, n,
                                    nk, spb, parts, z, zw, wlim, C, (uint32_t)g0);
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
             if (hipError_t e = launch_xor_parts(parts, blocks, nk, 32u * MT, (uint32_t)(8 * CG * gy), ans, 8ull * C,
@@ -1797,13 +1132,12 @@ hipError_t launch_mfma_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs,
     return hipSuccess;
 }
 
-// One key over the wide sliced DB (k_fold_sliced_direct_w): x * y <= cap.
-hipError_t launch_sliced_direct_w(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C,
-                                  uint32_t* parts, uint32_t* ans, hipStream_t st) {
+// One key over the sliced DB (k_fold_sliced_direct): x * y <= cap.
+hipError_t launch_sliced_direct(const uint32_t* bits, uint64_t wpk, const uint8_t* dbs, uint64_t nsg, uint32_t C,
+                                uint32_t* parts, uint32_t* ans, hipStream_t st) {
     const uint64_t cap = g_fold_blocks.load(std::memory_order_relaxed);
-    // parts[x][8 C words] of a launch: x * y * 32 bytes, far inside the partials area.
+    // parts[x][8 y words] of a launch: x * y * 32 bytes, far inside the partials area.
     const uint64_t gy_max = C < cap ? C : cap;
-    // (Default loads, as k_fold_sliced_direct: nontemporal ones measured slower for it.)
     for (uint64_t c0 = 0; c0 < C; c0 += gy_max) {
         const uint64_t gy = C - c0 < gy_max ? C - c0 : gy_max;
         uint64_t want = (uint64_t)cu_count_fold() * 8 / gy;
@@ -1811,7 +1145,7 @@ hipError_t launch_sliced_direct_w(const uint32_t* bits, uint64_t wpk, const uint
         uint64_t blocks, spb;
         split_chunks(nsg, want, 2, blocks, spb, cap / gy);
         if (blocks * gy > cap) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_fold_sliced_direct_w, dim3((uint32_t)blocks, (uint32_t)gy), dim3(256), 0, st, bits,
+        hipLaunchKernelGGL(k_fold_sliced_direct, dim3((uint32_t)blocks, (uint32_t)gy), dim3(256), 0, st, bits,
                            reinterpret_cast<const uint4*>(dbs), nsg, spb, parts, c0 == 0 ? ans : nullptr,
                            c0 == 0 ? 8ull * C : 0ull, wpk, C, (uint32_t)c0);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -1823,19 +1157,15 @@ hipError_t launch_sliced_direct_w(const uint32_t* bits, uint64_t wpk, const uint
 }
 }  // namespace
 
-hipError_t launch_pir_fold_sliced_wide(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
-                                       uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts,
-                                       hipStream_t st) {
+hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
+                                  uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st) {
     if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > kFoldMaxRecBytes) return hipErrorInvalidValue;
-    // 32-byte records: exactly the launches of the 32-byte entry.
-    if (rec_bytes == 32) return launch_pir_fold_sliced(bits, words_per_key, dbs, nrec, nkeys, ans, parts, st);
     if (nkeys == 0) return hipSuccess;
     if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, st);
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
     const uint64_t nsg = (nrec + 255) / 256;
     const uint32_t C = (uint32_t)(rec_bytes / 32);
-    if (nkeys <= (uint32_t)DPF_FOLD_SLICED_DIRECT)
-        return launch_sliced_direct_w(bits, words_per_key, dbs, nsg, C, parts, ans, st);
+    if (nkeys == 1) return launch_sliced_direct(bits, words_per_key, dbs, nsg, C, parts, ans, st);   // popcount fold, no MFMA
     // Columns per workgroup: the largest of 4, 2, 1 that divides C, capped
     // per tile shape below.  DPF_FOLD_WIDE_CG=<1|2|4> (measurement) caps it.
     static const int cg_env = [] {
@@ -1852,12 +1182,13 @@ hipError_t launch_pir_fold_sliced_wide(const uint32_t* bits, uint64_t words_per_
         uint32_t* a = ans + (uint64_t)k0 * 8 * C;
         hipError_t e;
 #define DPF_MW(MT_, NT_, SG_, CG_, WPE_) \
-    launch_mfma_w<MT_, NT_, SG_, CG_, WPE_>(b, words_per_key, dbs, nsg, C, nk, parts, a, zero, zw, st)
-        // Tile shapes as launch_pir_fold_sliced.  A column group of CG
-        // columns is 4 CG waves, so the shape has 512 / CG registers (less
-        // where two workgroups share a CU): the staged blocks shrink (SG)
-        // until nothing spills, and CG stops where that no longer works
-        // (register counts per instantiation: DESIGN §4.4).
+    launch_mfma<MT_, NT_, SG_, CG_, WPE_>(b, words_per_key, dbs, nsg, C, nk, parts, a, zero, zw, st)
+        // Tile shape per key count (32 keys per tile): MT key tiles x NT bit
+        // tiles per wave.  A column group of CG columns is 4 CG waves, so
+        // the shape has 512 / CG registers (less where two workgroups share
+        // a CU): the staged blocks shrink (SG) until nothing spills, and CG
+        // stops where that no longer works (register counts per
+        // instantiation: DESIGN §4.4).  32-byte records take the CG = 1 shapes.
         if (nk <= 32) e = cg == 4 ? DPF_MW(1, 2, 2, 4, 4) : cg == 2 ? DPF_MW(1, 2, 2, 2, 4) : DPF_MW(1, 2, 4, 1, 2);
         else if (nk <= 64) e = DPF_MW(2, 2, 2, 1, 2);   // CG = 2 (<2,2,4,2>, 2 waves per SIMD) measured no faster
         else if (nk <= 128) e = cg >= 2 ? DPF_MW(4, 2, 2, 2, 2) : DPF_MW(4, 2, 4, 1, 1);

@@ -5,7 +5,6 @@
 #include <stdint.h>
 
 #define DPF_FOLD_PLAN 1   // plan_fold() below (tools/fold_bench.hip)
-#define DPF_FOLD_WIDE 1   // the _wide launchers below (tools/fold_bench.hip)
 
 namespace dpfk {
 
@@ -29,32 +28,22 @@ uint64_t pir_fold_parts_bytes();
 hipError_t launch_pir_fold(const uint32_t* bits, uint64_t words_per_key, const uint8_t* db, uint64_t nrec,
                            uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st);
 
-// The MFMA fold (k_fold_mfma, 32-byte records): the same answers from the DB
-// in its bit-sliced layout (dbs, pir_sliced_bytes(nrec) bytes, built once by
-// launch_slice_db from the row-major DB).  Same bits / parts / ans contract
-// as launch_pir_fold.
-uint64_t pir_sliced_bytes(uint64_t nrec);
-hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint8_t* dbs, hipStream_t st);
-// sgm_keys > 0: the selection bits are super-group-major instead, in chunks
-// of sgm_g (1 or 4) super-groups: bits[S / g][sgm_keys][g * 8 words]
-// (S < ceil(nrec / 256)); key k of the batch is row k.
-hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
-                                  uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st,
-                                  uint32_t sgm_keys = 0, uint32_t sgm_g = 1);
-
-// The same for records of rec_bytes = 32 C bytes (a positive multiple of 32,
-// at most kFoldMaxRecBytes): the wide sliced layout dbs[S][c][n][g], column
-// c < C between the super-group and the bit position (C = 1: the layout
-// above), pir_sliced_bytes_wide(nrec, rec_bytes) bytes.  launch_slice_db_wide
-// of records [256 S0, ...) into dbs + S0 * 256 * rec_bytes writes what
-// slicing the whole DB writes there.  ans is [nkeys][rec_bytes]; bits / parts
-// as above.  rec_bytes == 32 makes exactly the 32-byte launchers' launches.
+// The matrix-core fold (k_fold_mfma; k_fold_sliced_direct for one key): the
+// same answers from the DB in its bit-sliced layout, for records of
+// rec_bytes = 32 C bytes (a positive multiple of 32, at most
+// kFoldMaxRecBytes):
+//   dbs[S][c][n][g] (u32), S = super-group of 256 records, c < C 32-byte
+//   column, n < 256 bit position of the column, g < 8 group of 32 records
+// (32-byte records: dbs[S][n][g]), pir_sliced_bytes(nrec, rec_bytes) bytes,
+// built once by launch_slice_db from the row-major DB.  launch_slice_db of
+// records [256 S0, ...) into dbs + S0 * 256 * rec_bytes writes what slicing
+// the whole DB writes there.  Same bits / parts / ans contract as
+// launch_pir_fold; ans is [nkeys][rec_bytes].
 constexpr uint64_t kFoldMaxRecBytes = 32768;
-uint64_t pir_sliced_bytes_wide(uint64_t nrec, uint64_t rec_bytes);
-hipError_t launch_slice_db_wide(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st);
-hipError_t launch_pir_fold_sliced_wide(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
-                                       uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts,
-                                       hipStream_t st);
+uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes);
+hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st);
+hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
+                                  uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st);
 
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per

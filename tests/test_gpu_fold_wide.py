@@ -120,6 +120,22 @@ def test_wide_slice_in_chunks_of_whole_super_groups():
     assert np.array_equal(whole, _layout(db))
 
 
+def test_slice_in_chunks_at_32_bytes():
+    """The same through the 32-byte entry: records [0, 512) and [512, 1000)
+    sliced into one buffer give the whole-DB slice."""
+    import torch
+    nrec = 1000
+    db = np.random.default_rng(3).integers(0, 256, (nrec, 32), dtype=np.uint8)
+    whole = torch.full((dpf.pir_db_sliced_size(nrec),), 0x5A, dtype=torch.uint8, device="cuda")
+    dpf.pir_db_slice_dev(_dev(db), nrec, whole)
+    d = torch.full((dpf.pir_db_sliced_size(nrec),), 0x5A, dtype=torch.uint8, device="cuda")
+    dpf.pir_db_slice_dev(_dev(db[:512]), 512, d)
+    dpf.pir_db_slice_dev(_dev(db[512:]), nrec - 512, d[512 * 32:])
+    torch.cuda.synchronize()
+    assert np.array_equal(d.cpu().numpy(), whole.cpu().numpy())
+    assert np.array_equal(whole.cpu().numpy(), _layout(db))
+
+
 # ---- 3. fold against the oracle's bits --------------------------------------
 # The one-key path, key tiles 1/2/4/8, a second 256-key pass, C = 1, 2, 3, 4,
 # 5, 8, 16, 32 and 33, ragged last super-groups, nrec = 0 and 1.
@@ -150,7 +166,7 @@ def test_wide_fold_matches_oracle(logN, nk, rec, nrec):
 # ---- 4. forced passes -------------------------------------------------------
 @pytest.mark.parametrize("max_blocks,max_sg,nk,rec,nrec", [
     (1, 1, 64, 64, 8192), (3, 5, 33, 96, 29993), (2, 3, 129, 256, 20000), (7, 2, 1, 128, 9999),
-    (5, 4, 300, 64, 12345),
+    (5, 4, 300, 64, 12345), (3, 5, 33, 32, 29993), (2, 3, 300, 32, 20000),
 ])
 def test_wide_fold_forced_passes(fold_limits, max_blocks, max_sg, nk, rec, nrec):
     rng = np.random.default_rng(nk * 7 + nrec + rec)

@@ -50,8 +50,8 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    // FOLD_MODE=mfma: the matrix-core fold over the bit-sliced DB (the wide
-    // layout and fold for rec_bytes > 32), built once here as the PIR server
+    // FOLD_MODE=mfma: the matrix-core fold over the bit-sliced DB (any
+    // rec_bytes that is a multiple of 32), built once here as the PIR server
     // does at load time; its answers must equal the Four-Russians / direct
     // fold's for every key.
     const bool mfma = getenv("FOLD_MODE") && getenv("FOLD_MODE")[0] == 'm';
@@ -61,17 +61,9 @@ int main(int argc, char** argv) {
     float slice_ms = 0;
     std::vector<uint8_t> ref((size_t)nkeys * rec_bytes);
     if (mfma) {
-#ifdef DPF_FOLD_WIDE
-        CK(hipMalloc(&dbs, dpfk::pir_sliced_bytes_wide(nrec, rec_bytes)));
+        CK(hipMalloc(&dbs, dpfk::pir_sliced_bytes(nrec, rec_bytes)));
         CK(hipEventRecord(e0, 0));
-        if (rec_bytes != 32) CK(dpfk::launch_slice_db_wide((const uint8_t*)db, nrec, rec_bytes, (uint8_t*)dbs, 0));
-        else CK(dpfk::launch_slice_db((const uint8_t*)db, nrec, (uint8_t*)dbs, 0));
-#else
-        if (rec_bytes != 32) { fprintf(stderr, "mfma mode: 32-byte records only\n"); return 2; }
-        CK(hipMalloc(&dbs, dpfk::pir_sliced_bytes(nrec)));
-        CK(hipEventRecord(e0, 0));
-        CK(dpfk::launch_slice_db((const uint8_t*)db, nrec, (uint8_t*)dbs, 0));
-#endif
+        CK(dpfk::launch_slice_db((const uint8_t*)db, nrec, rec_bytes, (uint8_t*)dbs, 0));
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         CK(hipEventElapsedTime(&slice_ms, e0, e1));
@@ -79,36 +71,10 @@ int main(int argc, char** argv) {
                                  (uint32_t*)ans, (uint32_t*)parts, 0));
         CK(hipMemcpy(ref.data(), ans, ref.size(), hipMemcpyDeviceToHost));
     }
-    // FOLD_SGM=1 (with FOLD_MODE=mfma): the selection bits super-group-major,
-    // sgm[S][key][8 words] = bits[key][8S .. 8S+8), as a tree pass could write them.
-    // FOLD_SGM=4: chunks of 4 super-groups, sgm[S/4][key][32 words] (one
-    // 128-byte line of a key per chunk, as the PIR tree kernel writes them).
-    const uint32_t sgm_g = mfma && getenv("FOLD_SGM") ? (uint32_t)atoi(getenv("FOLD_SGM")) : 0;
-    const bool sgm = sgm_g == 1 || sgm_g == 4;
-    void* bits_sgm = nullptr;
-    if (sgm) {
-        const uint64_t nsgs = (nrec + 255) / 256, nch = (nsgs + sgm_g - 1) / sgm_g;
-        std::vector<uint32_t> t(nch * sgm_g * nkeys * 8, 0);
-        for (uint64_t S = 0; S < nsgs; ++S)
-            for (uint32_t k = 0; k < nkeys; ++k)
-                for (int w = 0; w < 8; ++w)
-                    if (8 * S + w < wpk)
-                        t[((S / sgm_g * nkeys + k) * sgm_g + S % sgm_g) * 8 + w] = h[(size_t)k * wpk + 8 * S + w];
-        CK(hipMalloc(&bits_sgm, t.size() * 4));
-        CK(hipMemcpy(bits_sgm, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    }
     auto run = [&]() {
         CK(hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, 0));
-        if (sgm)
-            CK(dpfk::launch_pir_fold_sliced((const uint32_t*)bits_sgm, wpk, (const uint8_t*)dbs, nrec, nkeys,
-                                            (uint32_t*)ans, (uint32_t*)parts, 0, nkeys, sgm_g));
-#ifdef DPF_FOLD_WIDE
-        else if (mfma && rec_bytes != 32)
-            CK(dpfk::launch_pir_fold_sliced_wide((const uint32_t*)bits, wpk, (const uint8_t*)dbs, nrec, rec_bytes, nkeys,
-                                                 (uint32_t*)ans, (uint32_t*)parts, 0));
-#endif
-        else if (mfma)
-            CK(dpfk::launch_pir_fold_sliced((const uint32_t*)bits, wpk, (const uint8_t*)dbs, nrec, nkeys,
+        if (mfma)
+            CK(dpfk::launch_pir_fold_sliced((const uint32_t*)bits, wpk, (const uint8_t*)dbs, nrec, rec_bytes, nkeys,
                                             (uint32_t*)ans, (uint32_t*)parts, 0));
         else
             CK(dpfk::launch_pir_fold((const uint32_t*)bits, wpk, (const uint8_t*)db, nrec, rec_bytes, nkeys,
