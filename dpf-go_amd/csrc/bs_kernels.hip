@@ -25,14 +25,6 @@
 #include "aes_bytesliced.hpp"
 #include "bs_kernels.hpp"
 #include "dpf_kernels.hpp"
-#include "wave_prio.hpp"
-
-#ifndef DPF_BS_PRIO
-#define DPF_BS_PRIO 1   // issue priority by progress in k_evalfull_bs
-#endif
-#ifndef DPF_BS_FEEDBACK
-#define DPF_BS_FEEDBACK 0   // >0: 512-thread workgroups (every wave of a CU) and progress-feedback priority (A/B)
-#endif
 
 namespace dpfk {
 
@@ -203,7 +195,7 @@ __device__ __forceinline__ void leaf_store(uint32_t (&o)[32], uint32_t tl, const
         DST[4 * q_] = v_.x; DST[4 * q_ + 1] = v_.y; DST[4 * q_ + 2] = v_.z; DST[4 * q_ + 3] = v_.w; \
     }
 
-constexpr int kBsBlock = DPF_BS_FEEDBACK ? 512 : 256;
+constexpr int kBsBlock = 256;
 
 // Thread u: key u >> (flog - 3), frontier nodes 8*(u mod 2^(flog-3)) .. +7
 // of that key (level lvl0; 2^flog frontier nodes per key).  Output: 2^D
@@ -215,17 +207,7 @@ __global__ __launch_bounds__(kBsBlock, 2) void k_evalfull_bs(const uint4* __rest
                                                         uint32_t lvl0, uint64_t nthreads, uint8_t* __restrict__ out,
                                                         uint64_t out_stride) {
     const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-#if DPF_BS_FEEDBACK
-    __shared__ __attribute__((aligned(16))) uint32_t s_prog[64];
-    if (threadIdx.x < 64) s_prog[threadIdx.x] = 0xffffffffu;
-    __syncthreads();                               // before any wave returns or reads the slots
-    uint32_t pslot = 0;
-    uint32_t* prog = blockDim.x == 512u ? prog_slots(s_prog, pslot) : nullptr;
-#endif
     if (u >= nthreads) return;
-#if DPF_BS_FEEDBACK
-    if (prog) prog[pslot] = 0;
-#endif
     const uint32_t glog = flog - 3;
     uint64_t key = u >> glog;
     if constexpr (UNIFORM) key = __builtin_amdgcn_readfirstlane((uint32_t)key);
@@ -269,13 +251,11 @@ __global__ __launch_bounds__(kBsBlock, 2) void k_evalfull_bs(const uint4* __rest
     uint32_t S2[32];
     uint32_t tS0 = 0, tS1 = 0, tS2 = 0;
     uint32_t d = 0, path = 0;
-#if DPF_BS_PRIO
     // Issue priority by progress, as the T-table tree kernel's prio_step:
     // 3 until 3/4 of the lane's leaf-set pairs, 2, then 1 at 7/8.
     uint32_t pairs = 0;
     constexpr uint32_t kPairs = 1u << (D - 1);
     __builtin_amdgcn_s_setprio(3);
-#endif
     for (;;) {
         const uint32_t* cw = ek + (uint64_t)(lvl0 + d) * kBsRec;
         uint32_t L[32], R[32], B[32];
@@ -315,15 +295,9 @@ __global__ __launch_bounds__(kBsBlock, 2) void k_evalfull_bs(const uint4* __rest
             aes_mmo8(B, O, 0);
             leaf_store(O, tB, fcw, obase + (uint64_t)(path + 1) * 128, sig);
         }
-#if DPF_BS_PRIO
         ++pairs;
-#if DPF_BS_FEEDBACK
-        if (prog) prio_by_lead(prog, pslot, pairs, 1, DPF_BS_FEEDBACK);
-        else
-#endif
         if (pairs * 8 >= 7 * kPairs) __builtin_amdgcn_s_setprio(1);
         else if (pairs * 4 >= 3 * kPairs) __builtin_amdgcn_s_setprio(2);
-#endif
         path >>= 1;                               // back to X's own index at depth d
         while (d > 0 && (path & 1u)) {            // climb over finished right branches
             path >>= 1;
@@ -337,9 +311,6 @@ __global__ __launch_bounds__(kBsBlock, 2) void k_evalfull_bs(const uint4* __rest
         }
         path |= 1u;
     }
-#if DPF_BS_FEEDBACK
-    if (prog) prog[pslot] = 0xffffffffu;   // done: no longer the slowest
-#endif
 }
 
 hipError_t launch_unpack_bs(const uint8_t* keys, uint64_t key_len, uint64_t nkeys, uint32_t stop, uint32_t* ekb,

@@ -563,7 +563,7 @@ size_t pir_ek_bytes(size_t nkeys, uint32_t logN);
 size_t eval_work_bytes(size_t nkeys, size_t ppk, uint32_t logN);
 
 // Host-buffer batched Eval on one device, pipelined over chunks of keys:
-// caller xs -> pinned (CopyPool) -> HBM (d.hst) -> k_eval (d.st) -> pinned
+// caller xs -> pinned (CopyPool) -> HBM (d.hst) -> the Eval kernels (d.st) -> pinned
 // (d.cst) -> caller out, two slots per stage, so chunk i's kernel overlaps
 // the PCIe copies of its neighbours.
 int eval_on_device(Dev& d, const uint8_t* keys, size_t klen, size_t nk, const uint64_t* xs, size_t ppk,

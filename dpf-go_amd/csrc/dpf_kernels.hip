@@ -17,51 +17,12 @@
 #include <atomic>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 #include "aes_consts.hpp"
 #include "aes_ttable.hpp"
 #include "dpf_kernels.hpp"
 #include "wave_prio.hpp"
 #include "tree_ops.hpp"
-
-#ifndef DPF_COOP_WALK
-#define DPF_COOP_WALK 1
-#endif
-#ifndef DPF_QUAD_WALK
-#define DPF_QUAD_WALK 1  // shared walk: one block per quad of lanes on 4 waves (latency form, mmo_quad)
-#endif
-#ifndef DPF_QUAD_FAN
-#define DPF_QUAD_FAN 6   // log2 of the shared walk's paths in the quad form: 6 (4 waves) or 7 (8 waves)
-#endif
-#ifndef DPF_COOP_BFS
-#define DPF_COOP_BFS 0   // 1: the last W - 6 levels of the shared walk breadth-first in LDS (measured slower, r05)
-#endif
-#ifndef DPF_PAIR_STORES
-#define DPF_PAIR_STORES 1
-#endif
-#ifndef DPF_EVAL_STRIDE
-#define DPF_EVAL_STRIDE 0   // 1: k_eval2 grid = resident workgroups only (slower: 3667 vs 3489 us)
-#endif
-#ifndef DPF_EVAL_PAIRS
-#define DPF_EVAL_PAIRS 1   // batched Eval: two queries per thread (k_eval2)
-#endif
-#ifndef DPF_EVAL_BATCH
-#define DPF_EVAL_BATCH 1
-#endif
-#ifndef DPF_PRIO_STEPS
-#define DPF_PRIO_STEPS 3   // wave issue priority lowered by progress (prio_step)
-#endif
-#ifndef DPF_DEPTH_MODEL_COOP
-#define DPF_DEPTH_MODEL_COOP 1   // pick_shape prices the shared walk (latency once + W - 6 per thread)
-#endif
-#ifndef DPF_WALK_BATCH
-#define DPF_WALK_BATCH 1   // tree kernels' root-to-subtree walks: batched single-block rounds
-#endif
-#ifndef DPF_WALK_CW_LDS
-#define DPF_WALK_CW_LDS 1  // walks of a one-key workgroup read their correction words from LDS (staged once)
-#endif
-#ifndef DPF_DFS_CW_LDS
-#define DPF_DFS_CW_LDS 0   // ... and so does the subtree expansion below them (A/B)
-#endif
 
 namespace dpfk {
 
@@ -79,25 +40,9 @@ struct Ctx {
     uint4* nseed;       // node mode: seed cursor
     uint8_t* nt;        // node mode: t cursor
     uint32_t groups;    // 4-leaf groups finished (wave priority steps, prio_step)
-    const uint32_t* cwl;   // the key's CWs staged in LDS (8 words per level), or nullptr
-    bool sync = false;     // workgroup-uniform: every thread runs the same DFS (DPF_TREE_SYNC barriers)
-    uint32_t* prog = nullptr;   // DPF_PRIO_FEEDBACK: this SIMD's 16 wave-progress slots in LDS
+    uint32_t* prog = nullptr;   // feedback form: this SIMD's 16 wave-progress slots in LDS
     uint32_t pslot = 0;         // ... and this wave's slot (hardware wave id)
 };
-
-// Level lvl's correction word for the expansion: from the LDS copy when the
-// workgroup staged one (DPF_DFS_CW_LDS), else from the key.
-template <bool RAW>
-__device__ __forceinline__ CW ctx_cw(const Ctx& c, uint32_t lvl) {
-#if DPF_DFS_CW_LDS
-    if (c.cwl != nullptr) {
-        const uint4 a = *reinterpret_cast<const uint4*>(c.cwl + 8 * lvl);
-        const uint2 b = *reinterpret_cast<const uint2*>(c.cwl + 8 * lvl + 4);
-        return CW{{a.x, a.y, a.z, a.w}, b.x, b.y};
-    }
-#endif
-    return key_cw<RAW>(c.ks, lvl);
-}
 
 // Issue priority by progress.  A SIMD's waves issue oldest-first, so of the
 // 4 waves sharing one, the oldest finishes its subtree first and the
@@ -108,50 +53,31 @@ __device__ __forceinline__ CW ctx_cw(const Ctx& c, uint32_t lvl) {
 // thread's 4-leaf groups), so waves that are ahead yield the issue slots to
 // the ones behind and a SIMD's waves finish close together (busy 95%;
 // kernel 1048 -> 948 us on one box, profiles/r03/prio/).
-//   DPF_PRIO_STEPS 3: thresholds 3/4, 7/8, 15/16 (default);
-//   2: 1/2, 3/4, 7/8;  1: 1/4, 1/2, 3/4;  5: 7/8, 15/16, 31/32;  0: off.
-//   Subtrees of <= 2^5 leaf blocks (8 or fewer groups: the PIR tree, strong-
-//   scaling ranks) step at 1/2, 3/4, 7/8 (DPF_PRIO_STEPS_SMALL 2): at the
-//   PIR shape waves are busy 0.945-0.949 of the span instead of 0.914-0.922
-//   and the span is 244 vs 250-256 us (profiles/r04/prio/).
-#ifndef DPF_TREE_SYNC
-#define DPF_TREE_SYNC 0
-#endif
-#ifndef DPF_PRIO_FEEDBACK
-#define DPF_PRIO_FEEDBACK 3   // priority from the wave's lead over the slowest wave of its SIMD; 0: static steps
-#endif
-#ifndef DPF_PRIO_STEPS_SMALL
-#define DPF_PRIO_STEPS_SMALL 2
-#endif
+// Thresholds 3/4, 7/8, 15/16.  Subtrees of <= 2^5 leaf blocks (8 or fewer
+// groups: the PIR tree, strong-scaling ranks) step at 1/2, 3/4, 7/8: at the
+// PIR shape waves are busy 0.945-0.949 of the span instead of 0.914-0.922
+// and the span is 244 vs 250-256 us (profiles/r04/prio/).
+// Feedback form (c.prog set: one workgroup holds every wave of its CU):
+// priority from the wave's lead, in finished 4-leaf groups, over the slowest
+// wave of its SIMD (wave_prio.hpp).
+constexpr uint32_t kPrioFar = 3;   // prio_by_lead: a lead of 1 group is near, up to kPrioFar far
 template <int DMAX>
 __device__ __forceinline__ void prio_step(Ctx& c) {
-#if DPF_PRIO_FEEDBACK
-    // Feedback form (progress = finished 4-leaf groups).
     if (c.prog != nullptr) {
-        prio_by_lead(c.prog, c.pslot, ++c.groups, 1, DPF_PRIO_FEEDBACK);
+        prio_by_lead(c.prog, c.pslot, ++c.groups, 1, kPrioFar);
         return;
     }
-#endif
-#if DPF_PRIO_STEPS
-    constexpr int S = DMAX <= 5 ? DPF_PRIO_STEPS_SMALL : DPF_PRIO_STEPS;
+    constexpr bool small = DMAX <= 5;
     constexpr uint32_t total = DMAX >= 2 ? 1u << (DMAX - 2) : 1u;   // 4-leaf groups per thread
     const uint32_t d = ++c.groups;
-    constexpr uint32_t den = S == 1 ? 4 : S == 2 ? 8 : S == 5 ? 32 : 16;
-    constexpr uint32_t t1 = S == 1 ? 1 : S == 2 ? 4 : S == 5 ? 28 : 12;
-    constexpr uint32_t t2 = S == 1 ? 2 : S == 2 ? 6 : S == 5 ? 30 : 14;
-    constexpr uint32_t t3 = S == 1 ? 3 : S == 2 ? 7 : S == 5 ? 31 : 15;
+    constexpr uint32_t den = small ? 8 : 16;
+    constexpr uint32_t t1 = small ? 4 : 12;
+    constexpr uint32_t t2 = small ? 6 : 14;
+    constexpr uint32_t t3 = small ? 7 : 15;
     const uint32_t x = d * den;
     if (x >= t3 * total) __builtin_amdgcn_s_setprio(0);
     else if (x >= t2 * total) __builtin_amdgcn_s_setprio(1);
     else if (x >= t1 * total) __builtin_amdgcn_s_setprio(2);
-#else
-    (void)c;
-#endif
-#if DPF_TREE_SYNC
-    // Measurement: a workgroup barrier every DPF_TREE_SYNC groups keeps the
-    // workgroup's waves within one period of each other.
-    if (c.sync && (c.groups % DPF_TREE_SYNC) == 0) __syncthreads();
-#endif
 }
 
 __device__ __forceinline__ void emit_node(Ctx& c, const Node& n) {
@@ -183,10 +109,10 @@ __device__ __forceinline__ Blk bsel(bool b, const Blk& x, const Blk& y) {
 // loop body was ~85 KiB of code (22 AES-MMO bodies).
 template <bool B, bool RAW>
 __device__ __forceinline__ void leaves4(const Ctx& c, uint32_t lvl, const Node& n, uint8_t* p) {
-    CW cw = ctx_cw<RAW>(c, lvl);
+    CW cw = key_cw<RAW>(c.ks, lvl);
     Node L, R;
     expand<B>(c.tab, c.lo, n, cw, L, R);
-    CW cw1 = ctx_cw<RAW>(c, lvl + 1);
+    CW cw1 = key_cw<RAW>(c.ks, lvl + 1);
     Blk o0 = {}, o1 = {}, o2, o3;
     // Only the pending child stays live through the first iteration (a
     // select of L or R at the top of each iteration kept both live: 5 more
@@ -198,7 +124,7 @@ __device__ __forceinline__ void leaves4(const Ctx& c, uint32_t lvl, const Node& 
         Node a, b;
         expand<B>(c.tab, c.lo, m, cw1, a, b);
         Blk oa, ob;
-        mmo_pair<B>(c.tab, c.lo, KeyFixed<false>{}, a.s, oa, KeyFixed<false>{}, b.s, ob);
+        mmo2<B>(c.tab, c.lo, KeyFixed<false>{}, a.s, oa, KeyFixed<false>{}, b.s, ob);
         oa = leaf_fix(oa, a.t, c.fcw);
         ob = leaf_fix(ob, b.t, c.fcw);
         o2 = oa;
@@ -234,7 +160,7 @@ __device__ __forceinline__ void dfs(Ctx& c, uint32_t lvl0, const Node& n) {
         // apart left ~4 MiB of half-written lines per XCD (its whole L2) and
         // made WRITE_SIZE 1.26x the output.  Leaves are unchanged, only which
         // lane computes them.
-        CW cw = ctx_cw<RAW>(c, lvl0 + DMAX - 3);
+        CW cw = key_cw<RAW>(c.ks, lvl0 + DMAX - 3);
         Node L, R;
         expand<B>(c.tab, c.lo, n, cw, L, R);
         const bool odd = (threadIdx.x & 1u) != 0;
@@ -267,10 +193,10 @@ __device__ __forceinline__ void dfs(Ctx& c, uint32_t lvl0, const Node& n) {
         // Bottom two levels of a frontier at once: 4 seeds = 64 contiguous
         // bytes and their 4 t bytes as one 32-bit store (one byte store per
         // node made the NODES pass write 2.2x its 17 B per node).
-        CW cw = ctx_cw<RAW>(c, lvl0 + DMAX - 2);
+        CW cw = key_cw<RAW>(c.ks, lvl0 + DMAX - 2);
         Node L, R;
         expand<B>(c.tab, c.lo, n, cw, L, R);
-        CW cw1 = ctx_cw<RAW>(c, lvl0 + DMAX - 1);
+        CW cw1 = key_cw<RAW>(c.ks, lvl0 + DMAX - 1);
         Node q[4];
         expand<B>(c.tab, c.lo, L, cw1, q[0], q[1]);
         expand<B>(c.tab, c.lo, R, cw1, q[2], q[3]);
@@ -282,7 +208,7 @@ __device__ __forceinline__ void dfs(Ctx& c, uint32_t lvl0, const Node& n) {
         c.nt += 4;
         prio_step<DMAX>(c);
     } else if constexpr (D == 1) {
-        CW cw = ctx_cw<RAW>(c, lvl0 + DMAX - 1);
+        CW cw = key_cw<RAW>(c.ks, lvl0 + DMAX - 1);
         Node L, R;
         expand<B>(c.tab, c.lo, n, cw, L, R);
         if constexpr (NODES) {
@@ -290,13 +216,13 @@ __device__ __forceinline__ void dfs(Ctx& c, uint32_t lvl0, const Node& n) {
             emit_node(c, R);
         } else {
             Blk oL, oR;
-            mmo_pair<B>(c.tab, c.lo, KeyFixed<false>{}, L.s, oL, KeyFixed<false>{}, R.s, oR);
+            mmo2<B>(c.tab, c.lo, KeyFixed<false>{}, L.s, oL, KeyFixed<false>{}, R.s, oR);
             store16(c.outp, leaf_fix(oL, L.t, c.fcw));
             store16(c.outp + 16, leaf_fix(oR, R.t, c.fcw));
             c.outp += 32;
         }
     } else {
-        CW cw = ctx_cw<RAW>(c, lvl0 + DMAX - D);
+        CW cw = key_cw<RAW>(c.ks, lvl0 + DMAX - D);
         Node L, R;
         expand<B>(c.tab, c.lo, n, cw, L, R);
         // The right child is the only node live across the left subtree.
@@ -342,6 +268,8 @@ __global__ void k_unpack(const uint8_t* __restrict__ keys, uint64_t key_len, uin
 // written at out + key*out_stride + (u mod 2^units_log) * 16 * 2^D.
 // NODES: the same walk, but the 2^D nodes at level ltop + D are written to
 // (uint4*)out / out_t at [key*out_stride + (u mod 2^units_log) * 2^D].
+// Precondition: blockDim.x = 2^W, a power of two from 64 to kTreeBlockMax
+// (pick_block returns nothing else).
 template <int D, bool UNIFORM, bool NODES, bool RAW = false>
 __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const uint32_t* __restrict__ ekeys, uint32_t stop,
                                                         uint64_t nunits, uint32_t units_log, uint32_t ltop,
@@ -353,7 +281,8 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
     const uint64_t t_start = wall_clock64();
 #endif
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[kTabWords];
-    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // blockDim: 64..kTreeBlockMax
+    const uint32_t B = blockDim.x, W = 31u - (uint32_t)__builtin_clz(B);
+    const uint64_t u = (uint64_t)blockIdx.x * B + threadIdx.x;
     uint64_t key = u >> units_log;
     if constexpr (UNIFORM) key = __builtin_amdgcn_readfirstlane((uint32_t)key);
     const uint64_t local = u & ((1ull << units_log) - 1);
@@ -373,17 +302,12 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
     // level l's CW with vector loads issued before the table fill, and the
     // walks read it from LDS (in-order returns: no wait beyond the round's own).
     __shared__ __attribute__((aligned(16))) uint32_t s_cw[8 * 64];
-    const uint32_t Bw = blockDim.x;
-    const bool cw_lds = DPF_WALK_CW_LDS && UNIFORM && (Bw & (Bw - 1)) == 0 && stop <= 64 &&
-                        units_log >= 31u - (uint32_t)__builtin_clz(Bw) &&
-                        (uint64_t)blockIdx.x * Bw < nunits;   // workgroup-uniform
-    const bool cw_mine = cw_lds && threadIdx.x < (DPF_DFS_CW_LDS ? stop : ltop);
+    const bool cw_lds = UNIFORM && stop <= 64 && units_log >= W && (uint64_t)blockIdx.x * B < nunits;   // workgroup-uniform
+    const bool cw_mine = cw_lds && threadIdx.x < ltop;
     CW cw_pre{};
     if (cw_mine) cw_pre = key_cw<RAW>(c.ks, threadIdx.x);   // per-lane level: vector loads
-#if DPF_PRIO_FEEDBACK
     __shared__ __attribute__((aligned(16))) uint32_t s_prog[64];
     if (threadIdx.x < 64) s_prog[threadIdx.x] = 0xffffffffu;
-#endif
     fill_table_nobar(s_tab);
     if (cw_mine) {
         *reinterpret_cast<uint4*>(s_cw + 8 * threadIdx.x) = make_uint4(cw_pre.s.c0, cw_pre.s.c1, cw_pre.s.c2, cw_pre.s.c3);
@@ -396,25 +320,15 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
         const uint2 b = *reinterpret_cast<const uint2*>(s_cw + 8 * lvl + 4);
         return CW{{a.x, a.y, a.z, a.w}, b.x, b.y};
     };
-    // The shared walk below runs only in one-key workgroups, where cw_lds holds.
-    auto shared_cw = [&](uint32_t lvl) __attribute__((always_inline)) {
-        return DPF_WALK_CW_LDS ? lds_cw(lvl) : key_cw<RAW>(c.ks, lvl);
-    };
     c.groups = 0;
-    c.cwl = DPF_DFS_CW_LDS && cw_lds ? s_cw : nullptr;
-    c.sync = DPF_TREE_SYNC && UNIFORM && !NODES && (uint64_t)(blockIdx.x + 1) * Bw <= nunits;
-#if DPF_PRIO_FEEDBACK
-    // Only where the workgroup holds all 16 waves of its CU (one
+    // Feedback priority only where the workgroup holds all 16 waves of its CU (one
     // kTreeBlockBig-thread workgroup per CU): with two workgroups per CU a
     // wave sees half of its SIMD's waves, and steering by them was 3% slower.
-    if (UNIFORM && !NODES && D >= (int)kFeedbackMinD && Bw == 1024u) {
+    if (UNIFORM && !NODES && D >= (int)kFeedbackMinD && B == 1024u) {
         c.prog = prog_slots(s_prog, c.pslot);
         c.prog[c.pslot] = 0;
     }
-#endif
-#if DPF_PRIO_STEPS
     __builtin_amdgcn_s_setprio(3);
-#endif
     c.tab = reinterpret_cast<const uint8_t*>(s_tab);
     c.lo = (threadIdx.x & 31u) * 4u;
     if constexpr (NODES) {
@@ -429,35 +343,16 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
     n.s = key_root<RAW>(c.ks, n.t);
     uint32_t lvl = 0;
     if constexpr (UNIFORM) {
-        // Shared walk: when the whole workgroup (B = 2^W threads) evaluates
-        // consecutive subtrees of one key, its threads' paths agree on the
+        // Shared walk: when the whole workgroup evaluates consecutive
+        // subtrees of one key (cw_lds), its threads' paths agree on the
         // top ltop - W levels and fan out to B nodes below.  Wave 0 walks
         // 64 paths down to level l1 = ltop - W + 6 (one per group of B/64
         // threads) and leaves them in LDS; every thread then walks only the
         // last W - 6 levels.  Wave-AES per workgroup: l1 + (B/64)(W - 6)
         // instead of (B/64) ltop (configs[4]: 33 vs 96, configs[3]: 39 vs 144).
-        //
-        // Breadth-first finish (DPF_COOP_BFS, r05): instead of every thread
-        // walking the last W - 6 levels itself (8 waves x (W - 6) AES, with
-        // paths that share 1/2, 1/4, ... of their nodes), the workgroup
-        // expands the 64 nodes level by level in LDS: step s has 64 * 2^s
-        // parents, one expand (both children, dpf.go:227-240) on each of the
-        // first 2^s waves, so W - 6 = 3 steps are 1 + 2 + 4 wave-expands.  At
-        // the small per-rank shapes the per-thread walk was ~25% of the tree
-        // kernel's AES and ran with all 16 waves of a CU contending for LDS
-        // (tools/wave_times.hip, profiles/r05/wave_times: mean walk 25 us of a
-        // 51 us PIR-rank launch at N = 8).  Node j of step s sits in slot j
-        // (left child 2j, right 2j + 1), so after the last step slot i is
-        // thread i's subtree root.
-        constexpr uint32_t kFs = DPF_COOP_BFS ? kTreeBlockMax : (1u << (DPF_QUAD_FAN > 6 ? DPF_QUAD_FAN : 6));
+        constexpr uint32_t F = 6, kFs = 1u << F;   // paths of the shared walk: 2^F
         __shared__ uint32_t s_front[5 * kFs];   // SoA: word k of node j at k * kFs + j
-        const uint32_t B = blockDim.x;
-        const uint32_t W = 31u - (uint32_t)__builtin_clz(B);
-        if (DPF_COOP_WALK && (B & (B - 1)) == 0 && W >= 7 && units_log >= W && B <= (uint32_t)kTreeBlockMax &&
-            (cw_lds || !DPF_WALK_CW_LDS)) {   // uniform
-            // Paths of the shared walk: 2^F, F = 6, or DPF_QUAD_FAN with the
-            // quad form when the workgroup has the 4 * 2^F lanes for it.
-            const uint32_t F = DPF_QUAD_WALK && DPF_QUAD_FAN > 6 && W >= DPF_QUAD_FAN + 2 ? DPF_QUAD_FAN : 6;
+        if (W >= 7 && cw_lds) {   // uniform
             const uint32_t l1 = ltop - W + F;
             auto put = [&](uint32_t j, const Node& m) {
                 s_front[j] = m.s.c0; s_front[kFs + j] = m.s.c1; s_front[2 * kFs + j] = m.s.c2;
@@ -469,7 +364,7 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
                 m.t = s_front[4 * kFs + j];
                 return m;
             };
-            if (DPF_QUAD_WALK && W >= 8) {
+            if (W >= 8) {
                 // 2^F paths on the first 2^(F-4) waves, one quad of lanes per
                 // path (the latency form: the walk is serial, the CU nearly idle).
                 if (threadIdx.x < (4u << F)) {
@@ -479,7 +374,7 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
                     uint32_t col = j == 0 ? n.s.c0 : j == 1 ? n.s.c1 : j == 2 ? n.s.c2 : n.s.c3;
                     uint32_t t = n.t;
                     for (uint32_t i = 0; i < l1; ++i) {
-                        const CW cw = shared_cw(i);
+                        const CW cw = lds_cw(i);
                         const uint32_t cwj = j == 0 ? cw.s.c0 : j == 1 ? cw.s.c1 : j == 2 ? cw.s.c2 : cw.s.c3;
                         walk_step_quad(c.tab, c.lo, qk, j, col, t, cwj, cw.tl, cw.tr,
                                        (uint32_t)(subj >> (ltop - 1 - i)) & 1u);
@@ -491,53 +386,31 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
                 const uint64_t subj = (sub - threadIdx.x) + ((uint64_t)threadIdx.x << (W - 6));
                 Node m = n;
                 for (uint32_t i = 0; i < l1; ++i) {
-                    CW cw = shared_cw(i);
-                    walk_step<DPF_WALK_BATCH>(c.tab, c.lo, m, cw, (uint32_t)(subj >> (ltop - 1 - i)) & 1u);
+                    CW cw = lds_cw(i);
+                    walk_step<true>(c.tab, c.lo, m, cw, (uint32_t)(subj >> (ltop - 1 - i)) & 1u);
                 }
                 put(threadIdx.x, m);
             }
             __syncthreads();
-#if DPF_COOP_BFS
-            for (uint32_t st = 0; st < W - 6; ++st) {
-                const bool act = threadIdx.x < (64u << st);           // the first 2^st waves (uniform per wave)
-                Node m{};
-                if (act) m = get(threadIdx.x);
-                __syncthreads();                                       // every parent read before a child lands
-                if (act) {
-                    const CW cw = key_cw<RAW>(c.ks, l1 + st);
-                    Node L, R;
-                    expand<DPF_WALK_BATCH>(c.tab, c.lo, m, cw, L, R);
-                    put(2 * threadIdx.x, L);
-                    put(2 * threadIdx.x + 1, R);
-                }
-                __syncthreads();
-            }
-            n = get(threadIdx.x);
-            lvl = ltop;
-#else
             n = get(threadIdx.x >> (W - F));
             lvl = l1;
-#endif
         }
     }
     if (cw_lds) {
         for (uint32_t i = lvl; i < ltop; ++i)
-            walk_step<DPF_WALK_BATCH>(c.tab, c.lo, n, lds_cw(i), (uint32_t)(sub >> (ltop - 1 - i)) & 1u);
+            walk_step<true>(c.tab, c.lo, n, lds_cw(i), (uint32_t)(sub >> (ltop - 1 - i)) & 1u);
     } else {
         for (uint32_t i = lvl; i < ltop; ++i)
-            walk_step<DPF_WALK_BATCH>(c.tab, c.lo, n, key_cw<RAW>(c.ks, i), (uint32_t)(sub >> (ltop - 1 - i)) & 1u);
+            walk_step<true>(c.tab, c.lo, n, key_cw<RAW>(c.ks, i), (uint32_t)(sub >> (ltop - 1 - i)) & 1u);
     }
 #ifdef DPF_WAVE_TIMES
     const uint64_t t_walk = wall_clock64();
 #endif
     // Lane pairs share a key when a wave owns one key (UNIFORM): whole-line
-    // leaf stores (dfs PAIR).  DPF_PAIR_STORES=0 builds the r02 half-line
-    // stores for A/B runs.
-    constexpr bool kPair = DPF_PAIR_STORES && UNIFORM && !NODES && D >= 3;
+    // leaf stores (dfs PAIR).
+    constexpr bool kPair = UNIFORM && !NODES && D >= 3;
     dfs<D, D, NODES, kPair, UNIFORM, RAW>(c, ltop, n);
-#if DPF_PRIO_FEEDBACK
     if (c.prog != nullptr) c.prog[c.pslot] = 0xffffffffu;   // done: no longer the slowest
-#endif
 #ifdef DPF_WAVE_TIMES
     // Measurement build only (tools/wave_times.hip): per wave, start / end
     // (wall clock) and the hardware ids of the CU it ran on.
@@ -554,51 +427,13 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
 #endif
 }
 
-// Batched Eval: one thread per query, independent walks that compute only
-// the child on the path (the reference computes both children, dpf.go:184).
+// Batched Eval: independent walks that compute only the child on the path
+// (the reference computes both children, dpf.go:184), two queries per thread
+// (q = 2u, 2u + 1): the two walks run in lockstep (same start level and
+// length), so every AES round issues 32 lookups per wave instead of 16.
 // Without a frontier a walk starts at the root: stop+1 AES per query.  With
 // one (fseed != nullptr) it starts from the query's level-L node, written
 // by the NODES pass: stop-L+1 AES.  Output: one 0/1 byte per query.
-__global__ __launch_bounds__(kBlock, 4) void k_eval(const uint32_t* __restrict__ ekeys, uint32_t stop,
-                                                    uint32_t logN, const uint64_t* __restrict__ xs, uint64_t nq,
-                                                    uint64_t pts_per_key, const uint4* __restrict__ fseed,
-                                                    const uint8_t* __restrict__ ft, uint32_t L,
-                                                    uint8_t* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_tab[kTabWords];
-    fill_table(s_tab);
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // blockDim: 64..kBlock
-    if (q >= nq) return;
-    const uint64_t key = q / pts_per_key;
-    const uint32_t* ek = ekeys + key * ((uint64_t)(stop + 2) * 8);
-    const uint8_t* tab = reinterpret_cast<const uint8_t*>(s_tab);
-    const uint32_t lo = (threadIdx.x & 31u) * 4u;
-    const uint64_t x = xs[q];
-    Node n;
-    uint32_t lvl = 0;
-    if (fseed != nullptr) {
-        const uint64_t idx = (key << L) + ((x >> (logN - L)) & ((1ull << L) - 1));
-        const uint4 v = fseed[idx];
-        n.s = {v.x, v.y, v.z, v.w};
-        n.t = ft[idx];
-        lvl = L;
-    } else {
-        n.s = load_blk(ek);
-        n.t = ek[4];
-    }
-    for (uint32_t i = lvl; i < stop; ++i) {
-        CW cw = load_cw(ek, i);
-        walk_step<DPF_EVAL_BATCH>(tab, lo, n, cw, path_bit(x, logN - 1 - i));
-    }
-    Blk o = mmo1<DPF_EVAL_BATCH>(tab, lo, KeyFixed<false>{}, n.s);
-    o = leaf_fix(o, n.t, load_blk(ek + 8 + 8 * stop));
-    const uint32_t b = (uint32_t)(x & 127);
-    const uint32_t w = (b >> 5) == 0 ? o.c0 : (b >> 5) == 1 ? o.c1 : (b >> 5) == 2 ? o.c2 : o.c3;
-    out[q] = (uint8_t)((w >> (b & 31)) & 1u);
-}
-
-// Batched Eval, two queries per thread (q = 2u, 2u + 1): the two walks run
-// in lockstep (same start level and length), so every AES round issues 32
-// lookups per wave instead of 16.  Same output as k_eval.
 __device__ __forceinline__ Node eval_start(const uint32_t* ek, uint64_t key, uint64_t x, uint32_t logN,
                                            const uint4* fseed, const uint8_t* ft, uint32_t L) {
     Node n;
@@ -634,8 +469,7 @@ __device__ __forceinline__ uint64_t pair_key(uint64_t q, uint64_t pts_per_key) {
     return k;
 }
 // The pair's points and start nodes (frontier gathers): issued before the
-// workgroup fills its table, so their HBM latency overlaps the fill
-// (DPF_EVAL_EARLY; the first pair of every thread).
+// workgroup fills its table, so their HBM latency overlaps the fill.
 template <bool UNI>
 __device__ __forceinline__ PairIn eval_pair_in(const uint32_t* __restrict__ ekeys, uint32_t stop, uint32_t logN,
                                                const uint64_t* __restrict__ xs, uint64_t nq, uint64_t pts_per_key,
@@ -674,18 +508,18 @@ __device__ __forceinline__ uint32_t eval_pair_bits(const uint32_t* __restrict__ 
             const uint4 a = *reinterpret_cast<const uint4*>(cwp + 8 * (i - i0));
             const uint2 b = *reinterpret_cast<const uint2*>(cwp + 8 * (i - i0) + 4);
             const CW cw{{a.x, a.y, a.z, a.w}, b.x, b.y};
-            walk_step2<DPF_EVAL_BATCH>(tab, lo, p.n0, cw, path_bit(p.x0, logN - 1 - i), p.n1, cw,
+            walk_step2<true>(tab, lo, p.n0, cw, path_bit(p.x0, logN - 1 - i), p.n1, cw,
                                        path_bit(p.x1, logN - 1 - i));
         }
     } else {
         for (uint32_t i = i0; i < stop; ++i) {
             const CW cw0 = load_cw(ek0, i), cw1 = UNI ? cw0 : load_cw(ek1, i);
-            walk_step2<DPF_EVAL_BATCH>(tab, lo, p.n0, cw0, path_bit(p.x0, logN - 1 - i), p.n1, cw1,
+            walk_step2<true>(tab, lo, p.n0, cw0, path_bit(p.x0, logN - 1 - i), p.n1, cw1,
                                        path_bit(p.x1, logN - 1 - i));
         }
     }
     Blk o0, o1;
-    mmo2<DPF_EVAL_BATCH>(tab, lo, KeyFixed<false>{}, p.n0.s, o0, KeyFixed<false>{}, p.n1.s, o1);
+    mmo2<true>(tab, lo, KeyFixed<false>{}, p.n0.s, o0, KeyFixed<false>{}, p.n1.s, o1);
     const Blk f0 = UNI && cwp != nullptr ? load_blk(cwp + 8 * (stop - i0)) : load_blk(ek0 + 8 + 8 * stop);
     o0 = leaf_fix(o0, p.n0.t, f0);
     o1 = leaf_fix(o1, p.n1.t, UNI ? f0 : load_blk(ek1 + 8 + 8 * stop));
@@ -701,21 +535,6 @@ __device__ __forceinline__ void eval_pair_walk(const uint32_t* __restrict__ ekey
     if (q0 + 1 < nq) out[q0 + 1] = (uint8_t)(b >> 8);
 }
 
-#ifndef DPF_EVAL_EARLY
-#define DPF_EVAL_EARLY 1
-#endif
-#ifndef DPF_EVAL_PERSIST
-#define DPF_EVAL_PERSIST 1   // k_eval_persist for frontier Eval with wave-uniform keys (env DPF_EVAL_PERSIST=0: k_eval2)
-#endif
-#ifndef DPF_EVAL_FEEDBACK
-#define DPF_EVAL_FEEDBACK 3   // k_eval_persist: priority from the wave's lead over its SIMD's slowest; 0: fixed steps
-#endif
-#ifndef DPF_EVAL_CW_LDS
-#define DPF_EVAL_CW_LDS 1   // k_eval_persist: each pair's key records staged in LDS by LDS-DMA (A/B: 0)
-#endif
-#ifndef DPF_EVAL_PREFETCH
-#define DPF_EVAL_PREFETCH 0   // strided k_eval2: next pair's inputs requested before the current walk (A/B)
-#endif
 template <bool UNI>
 __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict__ ekeys, uint32_t stop,
                                                      uint32_t logN, const uint64_t* __restrict__ xs, uint64_t nq,
@@ -723,54 +542,17 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
                                                      const uint8_t* __restrict__ ft, uint32_t L,
                                                      uint8_t* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[kTabWords];
-    // Grid-stride loop.  launch_eval launches one thread per query pair
-    // (iters = 1); DPF_EVAL_STRIDE=1 caps the grid at the resident
-    // workgroups so each fills its 64 KiB table once, with the issue priority
-    // stepped down by progress like the tree kernels -- measured slower
-    // (3667 vs 3489 us at configs[2]): a thread's frontier gathers are then
-    // serialised, where short-lived waves overlap them.
-    const uint64_t stride = 2 * (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t first = 2 * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
-    const uint64_t iters = first < nq ? (nq - first + stride - 1) / stride : 0;
-#if DPF_EVAL_EARLY
-    // The first pair's points and frontier nodes are requested before the
-    // table fill (a short-lived wave otherwise waits out their HBM latency
-    // after it).
-    PairIn p0{};
-    if (iters) p0 = eval_pair_in<UNI>(ekeys, stop, logN, xs, nq, pts_per_key, fseed, ft, L, first);
-#endif
+    // One query pair per thread (launch_eval sizes the grid so): short-lived
+    // waves overlap their frontier gathers, where a grid capped at the
+    // resident workgroups serialised them (3667 vs 3489 us at configs[2]).
+    const uint64_t q0 = 2 * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    // The pair's points and frontier nodes are requested before the table
+    // fill (a short-lived wave otherwise waits out their HBM latency after it).
+    PairIn p{};
+    if (q0 < nq) p = eval_pair_in<UNI>(ekeys, stop, logN, xs, nq, pts_per_key, fseed, ft, L, q0);
     fill_table(s_tab);
     __builtin_amdgcn_s_setprio(3);
-#if DPF_EVAL_EARLY
-    if (iters) eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, first, p0);
-    const uint64_t it0 = 1;
-#else
-    const uint64_t it0 = 0;
-#endif
-#if DPF_EVAL_PREFETCH
-    // Strided form with the next pair's points and frontier nodes requested
-    // before the current pair's walk, so their HBM latency hides under it.
-    PairIn nx{};
-    if (it0 < iters) nx = eval_pair_in<UNI>(ekeys, stop, logN, xs, nq, pts_per_key, fseed, ft, L, first + it0 * stride);
-    for (uint64_t it = it0; it < iters; ++it) {
-        if (it * 16 >= 15 * iters) __builtin_amdgcn_s_setprio(0);
-        else if (it * 16 >= 14 * iters) __builtin_amdgcn_s_setprio(1);
-        else if (it * 16 >= 12 * iters) __builtin_amdgcn_s_setprio(2);
-        const uint64_t q0 = first + it * stride;
-        const PairIn cur = nx;
-        if (it + 1 < iters) nx = eval_pair_in<UNI>(ekeys, stop, logN, xs, nq, pts_per_key, fseed, ft, L, q0 + stride);
-        eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, q0, cur);
-    }
-#else
-    for (uint64_t it = it0; it < iters; ++it) {
-        if (it * 16 >= 15 * iters) __builtin_amdgcn_s_setprio(0);
-        else if (it * 16 >= 14 * iters) __builtin_amdgcn_s_setprio(1);
-        else if (it * 16 >= 12 * iters) __builtin_amdgcn_s_setprio(2);
-        const uint64_t q0 = first + it * stride;
-        eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, q0,
-                            eval_pair_in<UNI>(ekeys, stop, logN, xs, nq, pts_per_key, fseed, ft, L, q0));
-    }
-#endif
+    if (q0 < nq) eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, q0, p);
 }
 
 // Persistent batched Eval (r05): one 1024-thread workgroup per CU fills its
@@ -778,7 +560,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
 // frontier nodes move into per-wave LDS slots by LDS-DMA
 // (global_load_lds_dwordx4 / _dword) while the current pair walks, so they
 // cost no VGPRs (k_eval2 sits at the 128-VGPR limit; a register prefetch of
-// the next pair spilled and ran slower, DPF_EVAL_PREFETCH above) and no
+// the next pair spilled and ran slower) and no
 // workgroup waits out a fresh table fill or its first gathers.
 // Pipeline per thread, iteration i: read x(i) and node(i) from LDS; read
 // x(i+1), issue node(i+1)'s gathers; issue x(i+2); walk pair i.  The slots are
@@ -788,13 +570,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
 // UNI only: a wave's 64 pairs are 128 consecutive queries of one key, and nq
 // is even (pts_per_key % 128 == 0), so a pair's points are one 16-byte load.
 constexpr int kEvalPBlock = 1024;
+constexpr uint32_t kEvalPrioFar = 3;   // prio_by_lead every 4 pairs: a lead of 4 is near, up to 4 * kEvalPrioFar far
 struct EvalSlots {
     uint4 x[2][64];      // x(i), x(i+1): {x0, x1} as two uint64
     uint4 n0[64], n1[64]; // frontier seeds of pair i's two queries
     uint32_t t0[64], t1[64];   // aligned dwords holding their t bytes
-#if DPF_EVAL_CW_LDS
     uint32_t cw[2][64];  // pair i's key records, levels L..stop-1 and the final CW (parity of i)
-#endif
 };
 // s_waitcnt vmcnt(0) as a compiler memory barrier: the slot DMAs have
 // landed and no slot read is hoisted above the wait (hipcc's own waits did
@@ -849,9 +630,7 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
     };
     const uint64_t rec = (uint64_t)(stop + 2) * 8;
     const uint32_t ncw = (stop - L) * 8 + 4;
-    const bool cw_slots = DPF_EVAL_CW_LDS && ncw <= 64;      // uniform
-    (void)rec;
-    (void)cw_slots;
+    const bool cw_slots = ncw <= 64;      // uniform
     auto issue_x = [&](uint64_t i, int slot) __attribute__((always_inline)) {
         glds(xs + 2 * pair_of(i), &sl.x[slot][0], 16);
     };
@@ -866,12 +645,10 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
         glds(fseed + i1, &sl.n1[0], 16);
         glds(ft + (i0 & ~3ull), &sl.t0[0], 4);
         glds(ft + (i1 & ~3ull), &sl.t1[0], 4);
-#if DPF_EVAL_CW_LDS
         // The key's records from level L: 8 words per level, then the final
         // CW (dpf.go:186-188, :206), one word per lane.  Slot parity i & 1:
         // walk i - 2 (the slot's last reader) is done, by the wait above.
         if (cw_slots && lane < ncw) glds(ekeys + key * rec + 8 + 8 * L + lane, &sl.cw[slot][0], 4);
-#endif
     };
     // Pair i's points and nodes into registers, after vmcnt(0): the slot
     // DMAs, issued one walk earlier, and the previous pair's output stores,
@@ -895,20 +672,16 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
         return p;
     };
     if (iters == 0) return;                               // uniform over the grid
-#if DPF_EVAL_FEEDBACK
     // Wave-progress slots per SIMD, as the tree kernel's prio_step feedback form.
     __shared__ __attribute__((aligned(16))) uint32_t s_prog[64];
     if (threadIdx.x < 64) s_prog[threadIdx.x] = 0xffffffffu;
-#endif
     issue_x(0, 0);
     if (iters > 1) issue_x(1, 1);
     fill_table(s_tab);
     __builtin_amdgcn_s_setprio(3);
-#if DPF_EVAL_FEEDBACK
     uint32_t pslot;
     uint32_t* prog = prog_slots(s_prog, pslot);
     prog[pslot] = 0;
-#endif
     issue_nodes(0, 0);
     PairIn p = read_pair(0);
     if (iters > 1) issue_nodes(1, 1);
@@ -917,19 +690,9 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
         issue_x(2, 0);
     }
     for (uint64_t it = 0; it < iters; ++it) {
-#if DPF_EVAL_FEEDBACK
-        if ((it & 3) == 0) prio_by_lead(prog, pslot, (uint32_t)it, 4, 4 * DPF_EVAL_FEEDBACK);   // progress: pairs walked
-#else
-        if (it * 16 >= 15 * iters) __builtin_amdgcn_s_setprio(0);
-        else if (it * 16 >= 14 * iters) __builtin_amdgcn_s_setprio(1);
-        else if (it * 16 >= 12 * iters) __builtin_amdgcn_s_setprio(2);
-#endif
+        if ((it & 3) == 0) prio_by_lead(prog, pslot, (uint32_t)it, 4, 4 * kEvalPrioFar);   // progress: pairs walked
         const uint64_t pr = it * nthr + gt;
-#if DPF_EVAL_CW_LDS
         const uint32_t* cwp = cw_slots ? &sl.cw[it & 1][0] : nullptr;
-#else
-        const uint32_t* cwp = nullptr;
-#endif
         const uint32_t b = eval_pair_bits<true>(ekeys, stop, logN, nq, pts_per_key, fseed, L, s_tab, 2 * pair_of(it), p,
                                                 cwp);
         // unconditional (the last iteration rereads its own slots): a
@@ -946,9 +709,7 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
             issue_x(it + 3, (int)((it + 1) & 1));
         }
     }
-#if DPF_EVAL_FEEDBACK
     prog[pslot] = 0xffffffffu;
-#endif
 }
 
 #ifndef DPF_EVAL_TRIE_KERNEL
@@ -982,7 +743,7 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
 // AES per key at configs[2]: 1022 (frontier) + 4285 = 5307, against 6142 for
 // frontier + per-query walks; wave-AES per key 71 against 80 for k_eval2
 // (a wave runs its second AES of a level only if one of its lanes has two
-// nodes).  Output: one 0/1 byte per query, as k_eval.
+// nodes).  Output: one 0/1 byte per query, as k_eval2.
 constexpr uint32_t kTrieBlock = 512;        // threads per workgroup (one key)
 constexpr uint32_t kTrieCap = 1024;         // points per key (and nodes per level)
 constexpr uint32_t kTrieItems = kTrieCap / kTrieBlock;   // nodes per thread per level (2)
@@ -1121,16 +882,16 @@ __global__ __launch_bounds__(kTrieBlock, 4) void k_eval_trie(const uint32_t* __r
         // A wave runs the second AES of the level only if a lane has a
         // second node (ranks are dense: only the first waves do).
         if (__builtin_amdgcn_read_exec() & __ballot(has1)) {
-            walk_step2<DPF_EVAL_BATCH>(tab, lo, n[0], cw, side[0], n[1], cw, side[1]);
+            walk_step2<true>(tab, lo, n[0], cw, side[0], n[1], cw, side[1]);
             if (l == stop) {                                   // leaf blocks (dpf.go:214-224)
                 Blk oa, ob;
-                mmo2<DPF_EVAL_BATCH>(tab, lo, KeyFixed<false>{}, n[0].s, oa, KeyFixed<false>{}, n[1].s, ob);
+                mmo2<true>(tab, lo, KeyFixed<false>{}, n[0].s, oa, KeyFixed<false>{}, n[1].s, ob);
                 n[0].s = leaf_fix(oa, n[0].t, fcw);
                 n[1].s = leaf_fix(ob, n[1].t, fcw);
             }
         } else if (__builtin_amdgcn_read_exec() & __ballot(has0)) {
-            walk_step<DPF_EVAL_BATCH>(tab, lo, n[0], cw, side[0]);
-            if (l == stop) n[0].s = leaf_fix(mmo1<DPF_EVAL_BATCH>(tab, lo, KeyFixed<false>{}, n[0].s), n[0].t, fcw);
+            walk_step<true>(tab, lo, n[0], cw, side[0]);
+            if (l == stop) n[0].s = leaf_fix(mmo1<true>(tab, lo, KeyFixed<false>{}, n[0].s), n[0].t, fcw);
         }
         if (has0) {
             scr[tid] = make_uint4(n[0].s.c0, n[0].s.c1, n[0].s.c2, n[0].s.c3);
@@ -1168,7 +929,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_mmo_tt(const uint4* __restrict__ 
     const uint32_t lo = (threadIdx.x & 31u) * 4u;
     const uint4 va = in[2 * u], vb = in[2 * u + 1];
     Blk a = {va.x, va.y, va.z, va.w}, b = {vb.x, vb.y, vb.z, vb.w};
-    for (uint32_t r = 0; r < reps; ++r) mmo_pair<true>(tab, lo, KeyFixed<RIGHT>{}, a, a, KeyFixed<RIGHT>{}, b, b);
+    for (uint32_t r = 0; r < reps; ++r) mmo2<true>(tab, lo, KeyFixed<RIGHT>{}, a, a, KeyFixed<RIGHT>{}, b, b);
     out[2 * u] = make_uint4(a.c0, a.c1, a.c2, a.c3);
     out[2 * u + 1] = make_uint4(b.c0, b.c1, b.c2, b.c3);
 }
@@ -1198,20 +959,6 @@ hipError_t launch_unpack(const uint8_t* keys, uint64_t key_len, uint64_t nkeys, 
     return hipGetLastError();
 }
 
-template <int D, bool NODES>
-static hipError_t launch_full_d(const uint32_t* ek, uint32_t stop, uint64_t nunits, uint32_t units_log,
-                                uint32_t ltop, uint64_t sub_base, uint8_t* out, uint8_t* out_t,
-                                uint64_t out_stride, uint32_t block, hipStream_t st) {
-    const uint64_t blocks = (nunits + block - 1) / block;
-    if (units_log >= 6)
-        hipLaunchKernelGGL((k_evalfull<D, true, NODES>), dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop,
-                           nunits, units_log, ltop, sub_base, out, out_t, out_stride);
-    else
-        hipLaunchKernelGGL((k_evalfull<D, false, NODES>), dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop,
-                           nunits, units_log, ltop, sub_base, out, out_t, out_stride);
-    return hipGetLastError();
-}
-
 // CUs a launch may occupy: the calling thread's budget when the C ABI set
 // one (a stream created with a CU mask, dpf_stream_create_cu_masked), else
 // the device's.  Grid shapes (one round of resident waves, the depth model)
@@ -1228,15 +975,15 @@ int cu_count() {
     return cus;
 }
 
-// Workgroup size for a grid of n threads: full kTreeBlock-thread groups once
-// the grid covers every CU, otherwise the smallest power of two (>= one
-// wave) that spreads it over all CUs, so that a small batch is not packed
-// onto a few CUs whose LDS pipe then serialises it.
+// Workgroup size for a grid of n threads: full maxb-thread groups (maxb a
+// power of two) once the grid covers every CU, otherwise the smallest power
+// of two (>= one wave) that spreads it over all CUs, so that a small batch is
+// not packed onto a few CUs whose LDS pipe then serialises it.
 static uint32_t pick_block(uint64_t n, uint32_t maxb) {
     const uint64_t cus = (uint64_t)cu_count();
     uint32_t b = 64;
     while (b < maxb && n > cus * b) b <<= 1;
-    return b < maxb ? b : maxb;   // maxb need not be a power of two (occ5 variant: 640)
+    return b;
 }
 
 // Per-thread subtree depth D and workgroup size.  A thread walks span - D
@@ -1276,19 +1023,14 @@ static TreeShape pick_shape(uint32_t span, uint64_t nkeys, bool nodes, uint32_t 
         const double w = (double)threads(d) / wave_slots;                 // waves per CU
         const double rounds = w > 16.0 ? std::ceil(w / 16.0) : 1.0;
         const double per = w > 16.0 ? 16.0 * kPerWave : std::max(kLat, w * kPerWave);
-#if DPF_DEPTH_MODEL_COOP
-        // The shared workgroup walk (k_evalfull, DPF_COOP_WALK): one wave walks
-        // the top ltop - W + 6 levels alone (latency, once per round of
-        // workgroups), every thread the last W - 6.
-        const uint32_t bl = block(d);
-        const uint32_t W = 31u - (uint32_t)__builtin_clz(bl);
-        if (DPF_COOP_WALK && span - d >= 6 && (bl & (bl - 1)) == 0 && W >= 7 && span - d >= W) {
-            walk = DPF_COOP_BFS ? 0.0 : (double)(W - 6);               // BFS: W - 6 lightly loaded steps instead
-            lat = (double)(span + prefix_bits - d - W + 6 + (DPF_COOP_BFS ? W - 6 : 0)) * kLat;
+        // The shared workgroup walk (k_evalfull): one wave walks the top
+        // ltop - W + 6 levels alone (latency, once per round of workgroups),
+        // every thread the last W - 6.
+        const uint32_t W = 31u - (uint32_t)__builtin_clz(block(d));
+        if (W >= 7 && span - d >= W) {
+            walk = (double)(W - 6);
+            lat = (double)(span + prefix_bits - d - W + 6) * kLat;
         }
-#else
-        (void)prefix_bits;
-#endif
         const double work = walk + (nodes ? 2.0 : 3.0) * (double)(1u << d) - 2.0;   // NODES: no leaf AES
         const double t = rounds * (lat + work * std::max(kLat, per));
         if (t < best_t * 0.98) {          // prefer the deeper subtree on near-ties (less total work)
@@ -1299,33 +1041,61 @@ static TreeShape pick_shape(uint32_t span, uint64_t nkeys, bool nodes, uint32_t 
     return {best, block(best)};
 }
 
+// What a tree launch over the subtrees (prefix_bits, prefix) down to level
+// `depth` of every key derives from pick_shape; shared by the leaf, node and
+// raw-key launches and by evalfull_raw_ok.
+struct TreeLaunch {
+    uint32_t d;           // per-thread subtree depth
+    uint32_t ltop;        // levels walked per thread
+    uint32_t units_log;   // threads per key = 2^units_log
+    uint64_t nunits, sub_base;
+    dim3 grid, block;
+};
+static TreeLaunch tree_launch(uint64_t nkeys, uint32_t depth, uint32_t prefix_bits, uint64_t prefix, bool nodes) {
+    const TreeShape sh = pick_shape(depth - prefix_bits, nkeys, nodes, prefix_bits);
+    TreeLaunch t;
+    t.d = sh.d;
+    t.ltop = depth - sh.d;
+    t.units_log = t.ltop - prefix_bits;
+    t.nunits = nkeys << t.units_log;
+    t.sub_base = prefix << t.units_log;
+    t.grid = dim3((uint32_t)((t.nunits + sh.block - 1) / sh.block));
+    t.block = dim3(sh.block);
+    return t;
+}
+// f(std::integral_constant<int, D>) for the run-time depth d <= kMaxD.
+template <class F>
+static void with_depth(uint32_t d, F&& f) {
+    switch (d) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        default: return f(std::integral_constant<int, 7>{});
+    }
+}
+
 // Tree pass over every key: leaves of the subtree (prefix_bits, prefix) when
 // NODES is false, the 2^depth nodes at level `depth` (prefix 0) when true.
 template <bool NODES>
 static hipError_t launch_tree(const uint32_t* ek, uint64_t nkeys, uint32_t stop, uint32_t depth,
                               uint32_t prefix_bits, uint64_t prefix, uint8_t* out, uint8_t* out_t,
                               uint64_t out_stride, hipStream_t st) {
-    const uint32_t span = depth - prefix_bits;          // levels below the prefix node
-    const TreeShape sh = pick_shape(span, nkeys, NODES, prefix_bits);
-    const uint32_t d = sh.d;                             // per-thread subtree depth
-    const uint32_t ltop = depth - d;                     // levels walked per thread
-    const uint32_t units_log = ltop - prefix_bits;       // threads per key = 2^units_log
-    const uint64_t nunits = nkeys << units_log;
-    const uint64_t sub_base = prefix << units_log;
-    if (nunits == 0) return hipSuccess;
-#define DPF_LAUNCH(DD) \
-    return launch_full_d<DD, NODES>(ek, stop, nunits, units_log, ltop, sub_base, out, out_t, out_stride, sh.block, st)
-    switch (d) {
-        case 0: DPF_LAUNCH(0);
-        case 1: DPF_LAUNCH(1);
-        case 2: DPF_LAUNCH(2);
-        case 3: DPF_LAUNCH(3);
-        case 4: DPF_LAUNCH(4);
-        case 5: DPF_LAUNCH(5);
-        case 6: DPF_LAUNCH(6);
-        default: DPF_LAUNCH(7);
-    }
-#undef DPF_LAUNCH
+    const TreeLaunch t = tree_launch(nkeys, depth, prefix_bits, prefix, NODES);
+    if (t.nunits == 0) return hipSuccess;
+    with_depth(t.d, [&](auto dd) {
+        constexpr int D = decltype(dd)::value;
+        if (t.units_log >= 6)
+            hipLaunchKernelGGL((k_evalfull<D, true, NODES>), t.grid, t.block, 0, st, ek, stop, t.nunits, t.units_log,
+                               t.ltop, t.sub_base, out, out_t, out_stride);
+        else
+            hipLaunchKernelGGL((k_evalfull<D, false, NODES>), t.grid, t.block, 0, st, ek, stop, t.nunits, t.units_log,
+                               t.ltop, t.sub_base, out, out_t, out_stride);
+    });
+    return hipGetLastError();
 }
 
 // One-shot EvalFull straight from the key bytes (RAW): only where every wave
@@ -1338,37 +1108,20 @@ bool evalfull_raw_ok(uint64_t nkeys, uint32_t stop, uint32_t prefix_bits) {
         return !(e && e[0] == '0');
     }();
     if (!on || nkeys == 0 || prefix_bits > stop) return false;
-    const uint32_t span = stop - prefix_bits;
-    const TreeShape sh = pick_shape(span, nkeys, false, prefix_bits);
-    return span - sh.d >= 6;                             // units_log >= 6: UNIFORM
+    return tree_launch(nkeys, stop, prefix_bits, 0, false).units_log >= 6;   // UNIFORM
 }
 
 hipError_t launch_evalfull_raw(const uint8_t* keys, uint64_t klen, uint64_t nkeys, uint32_t stop, uint32_t prefix_bits,
                                uint64_t prefix, uint8_t* out, uint64_t out_stride, hipStream_t st) {
-    const uint32_t span = stop - prefix_bits;
-    const TreeShape sh = pick_shape(span, nkeys, false, prefix_bits);
-    const uint32_t d = sh.d, ltop = stop - d, units_log = ltop - prefix_bits;
-    if (units_log < 6) return hipErrorInvalidValue;
-    const uint64_t nunits = nkeys << units_log, sub_base = prefix << units_log;
-    const uint64_t blocks = (nunits + sh.block - 1) / sh.block;
+    const TreeLaunch t = tree_launch(nkeys, stop, prefix_bits, prefix, false);
+    if (t.units_log < 6) return hipErrorInvalidValue;
     // Aligned base below the batch, the batch's offset from it in kboff.
     const uint64_t kboff = (uintptr_t)keys & 3;
     const uint32_t* kw = reinterpret_cast<const uint32_t*>(keys - kboff);
-#define DPF_RAW(DD)                                                                                                  \
-    hipLaunchKernelGGL((k_evalfull<DD, true, false, true>), dim3((uint32_t)blocks), dim3(sh.block), 0, st, kw, stop, \
-                       nunits, units_log, ltop, sub_base, out, nullptr, out_stride, klen, kboff);                   \
-    break
-    switch (d) {
-        case 0: DPF_RAW(0);
-        case 1: DPF_RAW(1);
-        case 2: DPF_RAW(2);
-        case 3: DPF_RAW(3);
-        case 4: DPF_RAW(4);
-        case 5: DPF_RAW(5);
-        case 6: DPF_RAW(6);
-        default: DPF_RAW(7);
-    }
-#undef DPF_RAW
+    with_depth(t.d, [&](auto dd) {
+        hipLaunchKernelGGL((k_evalfull<decltype(dd)::value, true, false, true>), t.grid, t.block, 0, st, kw, stop,
+                           t.nunits, t.units_log, t.ltop, t.sub_base, out, nullptr, out_stride, klen, kboff);
+    });
     return hipGetLastError();
 }
 
@@ -1474,7 +1227,7 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
     // Persistent form (k_eval_persist): needs the frontier and wave-uniform keys.
     static const int persist = [] {
         const char* e = getenv("DPF_EVAL_PERSIST");
-        return e && *e ? atoi(e) : DPF_EVAL_PERSIST;
+        return e && *e ? atoi(e) : 1;
     }();
     // Its LDS-DMA stages a pair's two points with one 16-byte load from xs + 2*pair,
     // so it needs a 16-byte-aligned xs; an 8-byte-aligned one (a torch slice
@@ -1488,14 +1241,10 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
                            logN, xs, nq, pts_per_key, fseed, ft, L, out);
         return hipGetLastError();
     }
-#if DPF_EVAL_PAIRS
     const uint64_t nthreads = (nq + 1) / 2;
     const uint32_t block = pick_block(nthreads, kBlock);
-    uint64_t blocks = (nthreads + block - 1) / block;
-    // Resident workgroups only (64 KiB of table each: 2 per CU); k_eval2
-    // strides over the rest.
-    const uint64_t resident = 2 * (uint64_t)cu_count();
-    if (DPF_EVAL_STRIDE && blocks > resident) blocks = resident;
+    const uint64_t blocks = (nthreads + block - 1) / block;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;   // one pair per thread: no grid-stride loop to fall back on
     // Wave-uniform keys when every wave's 128 queries share one key.
     static const bool uni_on = [] {
         const char* e = getenv("DPF_EVAL_UNIFORM");
@@ -1507,12 +1256,6 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
     else
         hipLaunchKernelGGL(k_eval2<false>, dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop, logN, xs, nq,
                            pts_per_key, fseed, ft, L, out);
-#else
-    const uint32_t block = pick_block(nq, kBlock);
-    const uint64_t blocks = (nq + block - 1) / block;
-    hipLaunchKernelGGL(k_eval, dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop, logN, xs, nq, pts_per_key,
-                       fseed, ft, L, out);
-#endif
     return hipGetLastError();
 }
 

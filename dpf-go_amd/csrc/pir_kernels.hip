@@ -66,41 +66,10 @@ __device__ __forceinline__ void zero_answers(uint32_t* zero, uint64_t words) {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (uint64_t)gridDim.x * blockDim.x)
         zero[t] = 0;
 }
-// Issue priority by progress (as the tree kernels' prio_step): a SIMD's
-// waves issue oldest-first, so without it the oldest workgroup on a CU
-// finishes first and the youngest runs alone at the end.  Priority 3 until
-// 3/4 of the wave's range, then 2, 1 at 7/8, 0 at 15/16.
-__device__ __forceinline__ void fold_prio(uint64_t done, uint64_t all) {
-#if DPF_FOLD_PRIO
-    const uint64_t x = done * 16;
-    if (x >= 15 * all) __builtin_amdgcn_s_setprio(0);
-    else if (x >= 14 * all) __builtin_amdgcn_s_setprio(1);
-    else if (x >= 12 * all) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-#else
-    (void)done;
-    (void)all;
-#endif
-}
-// Workgroup barrier of the folds' LDS staging.  DPF_FOLD_RAW_BARRIER=1 fences
-// the local address space only (lgkmcnt) around s_barrier, so a global
-// prefetch issued before the barrier cannot be forced to land by it.  r05
-// measured it against __syncthreads(): identical (fold B=64 134.3 vs 134.3 us,
-// B=256 417 vs 416 us, PIR W=8 step 0.0765 vs 0.0765 ms;
-// profiles/r05/fold_barrier) -- the compiler already keeps the prefetch in
-// flight across __syncthreads -- so the default is the plain barrier.
-#ifndef DPF_FOLD_RAW_BARRIER
-#define DPF_FOLD_RAW_BARRIER 0
-#endif
-__device__ __forceinline__ void lds_barrier() {
-#if DPF_FOLD_RAW_BARRIER
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#else
-    __syncthreads();
-#endif
-}
+// Workgroup barrier of the folds' LDS staging: the plain barrier.  The
+// compiler keeps a global prefetch in flight across it; fencing the local
+// address space only measured identical (r05, profiles/r05/fold_barrier).
+__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -141,18 +110,6 @@ __device__ __forceinline__ uint2 valid_mask(uint64_t cc, uint64_t nrec, bool liv
 // wave takes every 4th chunk of the workgroup's contiguous range.  Lane l
 // always holds the same 16-byte position u = l mod 2C of its records, so its
 // accumulators are 4 words per key, XOR-reduced across lanes at the end.
-#ifndef DPF_WALK_BATCH_FZ
-#define DPF_WALK_BATCH_FZ 1   // k_pir_fused block-root walk: batched single-block rounds
-#endif
-#ifndef DPF_FZ_BATCH
-#define DPF_FZ_BATCH 0        // k_pir_fused producers: batched AES rounds (aes2_rounds<BATCH>)
-#endif
-#ifndef DPF_FZ_NOFOLD
-#define DPF_FZ_NOFOLD 0       // measurement only: folders take the ring entries without folding them
-#endif
-#ifndef DPF_FZ_TOUCH
-#define DPF_FZ_TOUCH 1        // k_pir_fused producers touch the next super-group into L2
-#endif
 // A streamed 16-byte operand; NT: a nontemporal load (the `nt` cache policy),
 // for DB slices too large to stay in the caches between batches (launch_mfma).
 typedef uint32_t fold_nt4 __attribute__((ext_vector_type(4)));
@@ -165,15 +122,7 @@ __device__ __forceinline__ uint4 fold_ld(const uint4* p) {
         return *p;
     }
 }
-#ifndef DPF_FOLD_PRIO
-#define DPF_FOLD_PRIO 1   // issue priority by progress (fold_prio)
-#endif
-#ifndef DPF_FOLD_SKEW_DEFAULT
-#define DPF_FOLD_SKEW_DEFAULT 62   // percent of a CU's chunk pair for its first k_fold4r workgroup (launch_4r)
-#endif
-#ifndef DPF_FOLD_PIPE
-#define DPF_FOLD_PIPE 1   // table pairs in flight per wave in k_fold4r's lookups (2: no gain, fold_bench r03)
-#endif
+constexpr int kFoldSkewDefault = 62;   // percent of a CU's chunk pair for its first k_fold4r workgroup (launch_4r)
 constexpr int kDWaves = 4;
 constexpr int kDirectMaxKeys = 16;
 
@@ -250,7 +199,6 @@ __global__ __launch_bounds__(64 * kDWaves) void k_fold_direct(const uint32_t* __
         }
     };
     for (uint64_t cp = c0 + w; cp < cend; cp += 2 * kDWaves) {
-        fold_prio(cp - c0, cend - c0);
 #pragma unroll
         for (int i = 0; i < 2 * C; i += 2) {
             step(cp, i, A0, B0, S0, A1, B1, S1);
@@ -415,17 +363,16 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 4 : 3) void k_fold4r(const uint3
             // Tables t and t + C share column cl: one 3-input XOR per word for
             // both (the bitop3 builtin also keeps the compiler from
             // re-associating the chain).  The 8 pairs are software-pipelined:
-            // pair p + kPipe's 4 reads are issued before pair p's XORs, with
+            // pair p + 1's 4 reads are issued before pair p's XORs, with
             // scheduling fences so the compiler keeps that order (left alone,
             // it reads one pair, waits, XORs: 4 reads in flight per wave).
+            // A second pair in flight gave no gain (fold_bench r03).
             auto slot = [&](uint32_t t) __attribute__((always_inline)) {
                 const uint32_t n = q * (16 / C) + t / C;
                 const uint32_t z = (n >> 3) ? z1 : z0;
                 return (z >> (4 * (n & 7))) & 15u;
             };
-            // Two pairs in flight where the registers allow (measured: no spills).
             constexpr int kPairs = 8;
-            constexpr int kPipe = (KW * C >= 8 && C < 8) || (WV == 8 && C >= 4) ? 1 : DPF_FOLD_PIPE;
             uint4 rd[kPairs][4];
             auto pair_t0 = [](int pi) { return (pi / C) * 2 * C + pi % C; };   // pair pi = tables (t0, t0 + C)
             auto issue = [&](int pi) __attribute__((always_inline)) {
@@ -436,11 +383,10 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 4 : 3) void k_fold4r(const uint3
                 rd[pi][2] = tab[(2 * t1) * 16 + (e1 ^ sw_row(t1, 0))];
                 rd[pi][3] = tab[(2 * t1 + 1) * 16 + (e1 ^ sw_row(t1, 1))];
             };
-#pragma unroll
-            for (int pi = 0; pi < kPipe; ++pi) issue(pi);
+            issue(0);
 #pragma unroll
             for (int pi = 0; pi < kPairs; ++pi) {
-                if (pi + kPipe < kPairs) issue(pi + kPipe);
+                if (pi + 1 < kPairs) issue(pi + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 const uint4 lo0 = rd[pi][0], hi0 = rd[pi][1], lo1 = rd[pi][2], hi1 = rd[pi][3];
                 uint32_t* a = acc[kg][pair_t0(pi) % C];
@@ -476,7 +422,6 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 4 : 3) void k_fold4r(const uint3
         if (cc < cend) fold(cc, q, cb, A, B);
     };
     for (uint64_t cb = c0; cb < cend; cb += Cfg::batch) {
-        fold_prio(cb - c0, cend - c0);
         lds_barrier();                                     // previous batch's selection reads are done
 #pragma unroll
         for (int kg = 0; kg < KW; ++kg) {
@@ -650,7 +595,7 @@ hipError_t launch_4r(const FoldArgs& a, uint64_t nchunks, uint64_t& blocks, hipS
     // for the first workgroup) shifts work to it.
     static const int skew = [] {
         const char* e = getenv("DPF_FOLD_SKEW");
-        return e ? atoi(e) : DPF_FOLD_SKEW_DEFAULT;
+        return e ? atoi(e) : kFoldSkewDefault;
     }();
     uint32_t nfirst = 0;
     uint64_t cpb_first = cpb;
@@ -895,7 +840,6 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
     // One staged block: its selection rows to LDS, the next block's loads
     // issued, then its super-groups folded.
     auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bn)[SG][NT]) __attribute__((always_inline)) {
-        fold_prio(sb - s0, s1 - s0);
         lds_barrier();                                          // previous block's operand reads are done
         store_sel(sv);
         lds_barrier();
@@ -1234,11 +1178,8 @@ hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, 
 // (walked once for all keys by folder wave 0 at the start, in LDS) 3 levels
 // down to each 32-pair piece of its range and expands only the nodes over
 // its pairs (fz_visit: one AES where the range leaves one child).
-#ifndef DPF_FZ_PRODONLY
-#define DPF_FZ_PRODONLY 0     // measurement only: 16 producer waves, no folders, no ring flow control
-#endif
-constexpr int kFzProd = DPF_FZ_PRODONLY ? 16 : 12;   // producer waves
-constexpr int kFzFold = DPF_FZ_PRODONLY ? 0 : 4;     // folder waves
+constexpr int kFzProd = 12;   // producer waves
+constexpr int kFzFold = 4;    // folder waves
 constexpr int kFzThreads = 64 * (kFzProd + kFzFold);
 constexpr uint32_t kFzBlockPairs = 256;      // leaf pairs (= DB super-groups) per workgroup
 constexpr uint32_t kFzBlockLog = 8;
@@ -1288,9 +1229,9 @@ template <bool ASYNC>
 __device__ __forceinline__ void fz_emit(FzCtx& c, const Node& n) {
     const CW cw = load_cw(c.ek, c.P);
     Node L, R;
-    expand<DPF_FZ_BATCH>(c.tab, c.lo, n, cw, L, R);
+    expand(c.tab, c.lo, n, cw, L, R);
     Blk oL, oR;
-    mmo_pair<DPF_FZ_BATCH>(c.tab, c.lo, KeyFixed<false>{}, L.s, oL, KeyFixed<false>{}, R.s, oR);
+    mmo2(c.tab, c.lo, KeyFixed<false>{}, L.s, oL, KeyFixed<false>{}, R.s, oR);
     oL = leaf_fix(oL, L.t, c.fcw);
     oR = leaf_fix(oR, R.t, c.fcw);
     const uint32_t m = c.live;
@@ -1298,15 +1239,13 @@ __device__ __forceinline__ void fz_emit(FzCtx& c, const Node& n) {
     // Touch the next pair's 8 KiB of the sliced DB (one 128-byte line per
     // lane) so the folders find it in L2 a period later; the value of the
     // previous touch is consumed here, long after it landed.
-#if DPF_FZ_TOUCH
     asm volatile("" ::"v"(c.touch));
     {
         const uint64_t s = c.sg + 1 < c.nsg ? c.sg + 1 : c.nsg - 1;
         c.touch = c.dbw[s * 2048 + (threadIdx.x & 63) * 32];
         c.sg += 1;
     }
-#endif
-    if constexpr (ASYNC && !DPF_FZ_PRODONLY) {
+    if constexpr (ASYNC) {
         // Slot i & 1 is free once every folder has folded this producer's
         // pair i - 2 (ring entry (i - 2) * kFzProd + p in folding order).
         if (i >= 2) {
@@ -1327,7 +1266,7 @@ __device__ __forceinline__ void fz_emit(FzCtx& c, const Node& n) {
             }
         }
     }
-    uint32_t* row = c.row + (DPF_FZ_PRODONLY ? 0 : (i & 1) * kFzSlot);
+    uint32_t* row = c.row + (i & 1) * kFzSlot;
     *reinterpret_cast<uint4*>(row) = make_uint4(oL.c0 & m, oL.c1 & m, oL.c2 & m, oL.c3 & m);
     *reinterpret_cast<uint4*>(row + 4) = make_uint4(oR.c0 & m, oR.c1 & m, oR.c2 & m, oR.c3 & m);
     if constexpr (ASYNC) {
@@ -1350,10 +1289,10 @@ __device__ __forceinline__ void fz_visit(FzCtx& c, const Node& n, uint32_t lo, u
         const bool needL = lo < half, needR = hi > half;
         Node L, R;
         if (needL && needR) {
-            expand<DPF_FZ_BATCH>(c.tab, c.lo, n, cw, L, R);
+            expand(c.tab, c.lo, n, cw, L, R);
         } else {
             L = n;
-            walk_step<DPF_FZ_BATCH>(c.tab, c.lo, L, cw, needR ? 1u : 0u);
+            walk_step(c.tab, c.lo, L, cw, needR ? 1u : 0u);
             R = L;
         }
         Node ch = L;
@@ -1376,7 +1315,7 @@ __global__ __launch_bounds__(kFzThreads, 1) void k_pir_fused(const uint32_t* __r
                                                             uint32_t* __restrict__ parts, uint32_t* __restrict__ zero,
                                                             uint64_t zero_words) {
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[kTabWords];
-    __shared__ __attribute__((aligned(16))) uint32_t s_ring[(DPF_FZ_PRODONLY ? 1 : 2) * kFzSlot];
+    __shared__ __attribute__((aligned(16))) uint32_t s_ring[2 * kFzSlot];
     __shared__ uint32_t s_top[64 * 5];
     __shared__ uint32_t s_prod[kFzProd], s_fold[4];
     if (threadIdx.x < kFzProd) s_prod[threadIdx.x] = 0;
@@ -1390,14 +1329,14 @@ __global__ __launch_bounds__(kFzThreads, 1) void k_pir_fused(const uint32_t* __r
     const uint32_t P = stop - 1;
     const uint32_t lb = P - kFzBlockLog;                      // level of the block root
     const uint32_t* kek = ek + (uint64_t)(l < nkeys ? l : 0) * ((uint64_t)(stop + 2) * 8);
-    if (wv == (DPF_FZ_PRODONLY ? 0 : kFzProd)) {
+    if (wv == kFzProd) {
         // Block root of every key: prefix bits, then the block index (dpf.go:183-201 path).
         const uint64_t path = (prefix << (lb - pb)) | blockIdx.x;
         Node n;
         n.s = load_blk(kek);
         n.t = kek[4];
         for (uint32_t i = 0; i < lb; ++i)
-            walk_step<DPF_WALK_BATCH_FZ>(tab, lo, n, load_cw(kek, i), (uint32_t)(path >> (lb - 1 - i)) & 1u);
+            walk_step<true>(tab, lo, n, load_cw(kek, i), (uint32_t)(path >> (lb - 1 - i)) & 1u);
         uint32_t* f = s_top + 5 * l;
         f[0] = n.s.c0; f[1] = n.s.c1; f[2] = n.s.c2; f[3] = n.s.c3; f[4] = n.t;
     }
@@ -1495,7 +1434,6 @@ __global__ __launch_bounds__(kFzThreads, 1) void k_pir_fused(const uint32_t* __r
 #pragma unroll
         for (int m = 0; m < 2; ++m) A[m] = *reinterpret_cast<const uint4*>(rows + (32 * m + r) * kFzRow + 4 * h);
         if constexpr (ASYNC) lds_release(s_fold + fw, q + 1);  // after the reads: the slot may be refilled
-        if (DPF_FZ_NOFOLD) return;
 #pragma unroll
         for (int t4 = 0; t4 < 4; ++t4) {
             fold_v8i bo[2];

@@ -8,10 +8,6 @@
 #include <stdint.h>
 #include "aes_ttable.hpp"
 
-#ifndef DPF_MMO_INTERLEAVE
-#define DPF_MMO_INTERLEAVE 1
-#endif
-
 namespace dpfk {
 
 struct Node {
@@ -99,28 +95,16 @@ __device__ __forceinline__ Blk key_fcw(const KeySrc& k, uint32_t stop) {
 }
 
 // prg (dpf.go:59-69) plus the parent's CW correction (dpf.go:230-238).
-// The two independent MMOs of a PRG call (or of a leaf pair), written as two
-// plain mmo1 calls so the scheduler interleaves them freely: 98.9 G blocks/s
-// in tools/aes_variants.hip, against 88.4 for a round-by-round interleave
-// and 93.3 fully serialized (r01 A/B, profiles/r01/full_ilp*).  An explicit
-// software pipeline (each block's 16 lookups issued while the other block's
-// are in flight, up to 32 per wave) was slower again: 93.1 vs 93.8 in-tree,
-// 21 VGPRs spilled (profiles/r02/pipe).
-template <bool B = false, class KA, class KB>
-__device__ __forceinline__ void mmo_pair(const uint8_t* tab, uint32_t lo, const KA& ka, Blk xa, Blk& oa,
-                                         const KB& kb, Blk xb, Blk& ob) {
-#if DPF_MMO_INTERLEAVE
-    mmo2<B>(tab, lo, ka, xa, oa, kb, xb, ob);
-#else
-    oa = mmo1(tab, lo, ka, xa);
-    ob = mmo1(tab, lo, kb, xb);
-#endif
-}
-
+// The two independent MMOs of a PRG call (like those of a leaf pair) go
+// through mmo2 (aes_ttable.hpp aes2_rounds): the two blocks' rounds
+// interleaved, or with B both blocks' 32 lookups of a round issued before any
+// XOR, where the registers allow it.  An explicit software pipeline (each
+// block's 16 lookups issued while the other block's are in flight) was
+// slower: 93.1 vs 93.8 in-tree, 21 VGPRs spilled (profiles/r02/pipe).
 template <bool B = false>
 __device__ __forceinline__ void expand(const uint8_t* tab, uint32_t lo, const Node& n, const CW& cw, Node& L,
                                        Node& R) {
-    mmo_pair<B>(tab, lo, KeyFixed<false>{}, n.s, L.s, KeyFixed<true>{}, n.s, R.s);
+    mmo2<B>(tab, lo, KeyFixed<false>{}, n.s, L.s, KeyFixed<true>{}, n.s, R.s);
     uint32_t tL = L.s.c0 & 1u, tR = R.s.c0 & 1u;
     L.s.c0 &= ~1u;
     R.s.c0 &= ~1u;
@@ -150,13 +134,7 @@ template <bool B = false>
 __device__ __forceinline__ void walk_step2(const uint8_t* tab, uint32_t lo, Node& n0, const CW& cw0, uint32_t bit0,
                                            Node& n1, const CW& cw1, uint32_t bit1) {
     Blk c0, c1;
-#if DPF_EXP_NOSEL
-    // Measurement only (wrong answers): the walk with a wave-uniform key, to
-    // bound what the per-lane key select costs.
-    mmo2<B>(tab, lo, KeyFixed<false>{}, n0.s, c0, KeyFixed<false>{}, n1.s, c1);
-#else
     mmo2<B>(tab, lo, KeySel{bit0 ? 0xffffffffu : 0u}, n0.s, c0, KeySel{bit1 ? 0xffffffffu : 0u}, n1.s, c1);
-#endif
     walk_fix(n0, c0, cw0, bit0);
     walk_fix(n1, c1, cw1, bit1);
 }

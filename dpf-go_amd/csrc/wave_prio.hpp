@@ -1,6 +1,6 @@
 // wave_prio.hpp — wave issue priority from progress feedback (device code),
-// shared by the T-table tree kernel, the persistent batched-Eval kernel
-// (dpf_kernels.hip) and the byte-sliced tree kernel (bs_kernels.hip).
+// shared by the T-table tree kernel and the persistent batched-Eval kernel
+// (dpf_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

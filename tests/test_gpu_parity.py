@@ -330,3 +330,68 @@ def test_eval_dev_points_at_8_byte_offset():
                                           d_out.data_ptr(), d_work.data_ptr(), d_work.numel(), st.cuda_stream)
         dpf._check(rc)
     assert e.value.code == dpf.DPF_ERR_PARAM
+
+
+_DEPTH_CHILD = r'''
+import sys
+sys.modules["torch"] = None          # the child needs none: dpf.lib() then loads the library alone
+sys.path[:0] = [%r, %r]
+import numpy as np, dpf, oracle
+from dpf import synth
+assert dpf.gpu_init(1) >= 1
+dpf.set_small_call_path("gpu")
+def keys(nk, logN, first):
+    al, s0, s1 = synth.key_seeds(nk, logN, first=first)
+    return (al,) + tuple(dpf.gen_batch_seeded(al, logN, s0, s1))
+_, ka, kb = keys(1, 24, 2400)
+for k in (ka, kb):
+    assert np.array_equal(dpf.evalfull_batch(k, 24, ngpus=1), oracle.evalfull_batch(k, 24, nthreads=8)), "1 x 2^24"
+al, ka, kb = keys(70, 16, 1600)
+xs = synth.eval_points(70, 256, 16)
+xs[:, 0] = al
+for k in (ka, kb):
+    assert np.array_equal(dpf.evalfull_batch(k, 16, ngpus=1), oracle.evalfull_batch(k, 16, nthreads=8)), "70 x 2^16"
+    assert np.array_equal(dpf.eval_batch(k, xs, 16, ngpus=1), oracle.eval_batch(k, xs, 16, nthreads=8)), "eval"
+dpf.gpu_shutdown()
+print("done")
+'''
+
+
+@pytest.mark.parametrize("raw", [None, "0"], ids=["raw", "expanded"])
+@pytest.mark.parametrize("depth", range(8))
+def test_every_subtree_depth(depth, raw):
+    """Every per-thread subtree depth D of the tree kernel (DPF_SUBTREE_DEPTH=D),
+    from raw key bytes and (DPF_RAW_KEYS=0) from expanded records, both
+    shares against the oracle byte for byte.  A fresh child per case: the two
+    switches are read once per process.  The shapes are the smallest that
+    reach every form of k_evalfull on a 256-CU device (pick_shape /
+    pick_block evaluated on the host):
+
+      EvalFull, 1 key, logN 24 (stop 17): one-key workgroups, CWs from LDS
+        D   threads  workgroup  shared walk
+        0   131072   512        one quad of lanes per path (W = 9)
+        1    65536   256        one quad of lanes per path (W = 8)
+        2    32768   128        one lane per path (W = 7)
+        3+   16384..1024  64    none
+      EvalFull, 70 keys, logN 16 (stop 9)
+        0    35840   256        quad; two workgroups per key
+        1    17920   128        one lane per path
+        2, 3  8960, 4480  64    none; wave-uniform keys, one wave per workgroup
+        4..7  2240..280   64    none; 32..4 threads per key: per-lane keys
+      Eval, 70 keys x 256 points, logN 16: node pass to level 7 (depth min(D, 7)),
+        128..1 threads per key (wave-uniform for D <= 1), then the persistent
+        walk kernel; every key's alpha is among its points.
+
+    Raw key bytes are read where stop - D >= 6 (all of the 1-key case, D <= 3
+    of the 70-key case), expanded records elsewhere and in the node pass."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, DPF_SUBTREE_DEPTH=str(depth))
+    env.pop("DPF_RAW_KEYS", None)
+    if raw is not None:
+        env["DPF_RAW_KEYS"] = raw
+    code = _DEPTH_CHILD % (os.path.join(root, "dpf-go_amd"), os.path.join(root, "oracle"))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.strip().endswith("done")
