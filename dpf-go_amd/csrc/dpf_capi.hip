@@ -29,6 +29,7 @@
 #include "bs_kernels.hpp"
 #include "dpf_kernels.hpp"
 #include "pir_kernels.hpp"
+#include "pir_update_plan.hpp"
 
 using dpfh::full_len;
 using dpfh::key_len;
@@ -1196,6 +1197,34 @@ int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, si
     return DPF_OK;
 }
 
+// Records of the sliced DB changed / read back in place: every argument is
+// checked before any device call.
+static int check_update_bufs(size_t rec_bytes, const void* d_dbs, const void* d_idx, const void* d_recs) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (!d_dbs || !d_idx || !d_recs) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_dbs | (uintptr_t)d_recs) % 16 != 0 || (uintptr_t)d_idx % 8 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    return DPF_OK;
+}
+
+int dpf_pir_db_update_sliced_wide_dev(int device, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, const uint64_t* d_idx,
+                                      const uint8_t* d_recs, size_t n, void* stream) {
+    if (int rc = check_update_bufs(rec_bytes, d_dbs, d_idx, d_recs)) return rc;
+    if (n == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_update_sliced(d_dbs, nrec, rec_bytes, d_idx, d_recs, n, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                      const uint64_t* d_idx, size_t n, uint8_t* d_out, void* stream) {
+    if (int rc = check_update_bufs(rec_bytes, d_dbs, d_idx, d_out)) return rc;
+    if (n == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_gather_sliced(d_dbs, nrec, rec_bytes, d_idx, n, d_out, (hipStream_t)stream));
+    return DPF_OK;
+}
+
 int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
                                  const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
                                  void* stream) {
@@ -1363,6 +1392,82 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
     for (int i = 0; i < g; ++i)
         for (size_t b = 0; b < nkeys * rb; ++b) ans[b] ^= part[(size_t)i][b];
     return DPF_OK;
+}
+
+uint64_t dpf_pir_db_nrec(void* handle) { return handle ? ((PirDb*)handle)->nrec : 0; }
+
+// One chunk of a shard's planned entries [a, b): the local indices and (for
+// an update) the records go up through the device's staging buffers, the
+// device form runs on the device's stream under its mutex, and the call
+// returns when the stream is idle: a concurrent dpf_pir_answer sees the shard
+// before or after the chunk, never in between.
+static int pir_update_chunk(PirDb* h, size_t s, const dpfh::PirUpdatePlan& plan, size_t a, size_t b,
+                            const uint8_t* recs, uint8_t* out, std::vector<uint8_t>& host) {
+    const size_t rb = h->rec_bytes, m = b - a;
+    Dev& d = *h->devs[s];
+    uint8_t* db = (uint8_t*)h->shard[s];
+    const uint64_t nrec = h->shard_n[s];
+    // Entries that are consecutive in the caller's arrays (sorted input) go
+    // up / come back straight from / to them; otherwise through `host`.
+    bool direct = true;
+    for (size_t k = 1; direct && k < m; ++k) direct = plan.src[a + k] == plan.src[a] + k;
+    uint8_t* stage = nullptr;
+    if (direct) {
+        stage = recs ? const_cast<uint8_t*>(recs) + plan.src[a] * rb : out + plan.src[a] * rb;
+    } else {
+        host.resize(m * rb);
+        stage = host.data();
+        if (recs)
+            for (size_t k = 0; k < m; ++k) memcpy(stage + k * rb, recs + plan.src[a + k] * rb, rb);
+    }
+    std::lock_guard<std::mutex> lk(d.mu);
+    DeviceGuard gd(d.id);
+    HIP_TRY(hipError_t(d.xs.ensure(m * 8)));
+    HIP_TRY(hipError_t(d.out.ensure(m * rb)));
+    const uint64_t* d_idx = (const uint64_t*)d.xs.p;
+    HIP_TRY(hipMemcpyAsync(d.xs.p, plan.local.data() + a, m * 8, hipMemcpyHostToDevice, d.st));
+    if (recs) {
+        HIP_TRY(hipMemcpyAsync(d.out.p, stage, m * rb, hipMemcpyHostToDevice, d.st));
+        HIP_TRY((h->sliced ? dpfk::launch_update_sliced : dpfk::launch_update_rows)(db, nrec, rb, d_idx,
+                                                                                    (const uint8_t*)d.out.p, m, d.st));
+    } else {
+        HIP_TRY((h->sliced ? dpfk::launch_gather_sliced : dpfk::launch_gather_rows)(db, nrec, rb, d_idx, m,
+                                                                                    (uint8_t*)d.out.p, d.st));
+        HIP_TRY(hipMemcpyAsync(stage, d.out.p, m * rb, hipMemcpyDeviceToHost, d.st));
+    }
+    HIP_TRY(hipStreamSynchronize(d.st));
+    if (d.out.cap > 2 * kStageBytes) d.out.release();   // a large chunk's staging is not kept
+    if (d.xs.cap > kStageBytes) d.xs.release();
+    if (out && !direct)
+        for (size_t k = 0; k < m; ++k) memcpy(out + plan.src[a + k] * rb, stage + k * rb, rb);
+    return DPF_OK;
+}
+
+// dpf_pir_db_update (recs) and dpf_pir_db_read (out): plan on the host, then
+// shard by shard in chunks of at most kPirUploadChunk bytes of records.
+static int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const uint8_t* recs, uint8_t* out) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (n == 0) return DPF_OK;
+    if (!idx || (!recs && !out)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    dpfh::PirUpdatePlan plan;
+    if (!dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan))
+        return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
+    const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->rec_bytes);
+    std::vector<uint8_t> host;
+    for (size_t s = 0; s + 1 < plan.shard_off.size(); ++s)
+        for (size_t a = plan.shard_off[s]; a < plan.shard_off[s + 1]; a += chunk)
+            if (int rc = pir_update_chunk(h, s, plan, a, std::min(a + chunk, plan.shard_off[s + 1]), recs, out, host))
+                return rc;
+    return DPF_OK;
+}
+
+int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, size_t n) {
+    return pir_update_or_read(handle, idx, n, recs, nullptr);
+}
+
+int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out) {
+    return pir_update_or_read(handle, idx, n, nullptr, out);
 }
 
 void dpf_pir_db_free(void* handle) { delete (PirDb*)handle; }

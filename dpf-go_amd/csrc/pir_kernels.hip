@@ -974,6 +974,253 @@ hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes,
     return hipSuccess;
 }
 
+// ---- records of a resident DB changed and read back in place --------------
+// A record's 256 C bits lie in 256 C different words of the sliced layout, one
+// bit in each, so an update is a read-modify-write of whole tiles: tile
+// (S, c) = dbs[S][c][0..255][0..7], 8 KiB contiguous.  Owner form, no atomics:
+// the updates come sorted by record index, so those of one super-group are a
+// contiguous run idx[h .. e), and the workgroup of the run's head h rewrites
+// tile (S, c) alone.  Thread n of its 256 loads its row dbs[S][c][n][0..7]
+// (two uint4, the access pattern of k_fold_sliced_direct), walks the run --
+// for update i it replaces bit j = idx & 31 of word g = (idx & 255) >> 5 with
+// bit n of column c of recs[i] (g, j wave-uniform; bit n of a column is bit
+// n & 31 of its little-endian word n >> 5, so a wave needs two words per
+// update) -- and stores the row back.  Later updates overwrite earlier ones
+// in the registers: of equal indices the last wins.
+//
+// Grid: workgroup b = (slot, column c) = (b / C, b % C) takes a chunk of K
+// consecutive updates.  For K > 1, slot -> chunk deals each eighth of the
+// chunks to one residue of slot % 8: workgroups go round-robin over the 8
+// XCDs, and the heads of a dense run come at a fixed stride (every 256 / K
+// chunks), a multiple of 8 for 32-byte records, so chunk = slot would run
+// every tile of such a run on one XCD.  Lane l < K tests update i = i0 + l for being a head (i == 0 or
+// idx[i-1] >> 8 != idx[i] >> 8, and idx[i] < nrec: entries past nrec are
+// skipped, so the padding of the last super-group stays zero) and the
+// workgroup takes the chunk's heads one after the other; a run may extend
+// past the chunk, it belongs to its head.  K = 1 is one workgroup per (update,
+// column), which exits unless the update is a head; the launcher raises K
+// with the least possible mean run length n / ceil(nrec / 256), so that dense
+// updates do not launch 255 idle workgroups per tile.  The run is walked 64
+// entries at a time: lane l of every wave loads idx[i + l] (a ballot finds
+// the run's end) and its wave's two words of recs[i + l], and the walk takes
+// (g, j) and the two words of each update by v_readlane, so a run costs one
+// round of loads per 64 updates, not one per update.  Where the entries of
+// such a batch are consecutive records (a dense run), 64 ballots transpose
+// the batch as k_slice_db does -- thread n gets the 64 new bits of its bit
+// position at once -- and two shifts per word deposit them: ~5 VALU per
+// update instead of ~27.  With unsorted input two workgroups may rewrite one
+// tile (content unspecified), but S comes from an idx < nrec and record loads
+// from i < n: no access leaves the buffers.  Sparse updates are bound by the
+// three dependent round trips of a tile (index, tile and record loads), so
+// the kernel is held to 8 waves per SIMD (measurements: profiles/pir_update).
+constexpr uint32_t kUpdSeqMin = 16;   // consecutive updates of a batch from which the ballot form is cheaper
+__global__ __launch_bounds__(256, 8) void k_update_sliced(uint4* __restrict__ dbs, uint64_t nrec, uint32_t ncols,
+                                                        const uint64_t* __restrict__ idx,
+                                                        const uint32_t* __restrict__ recs, uint64_t n, uint64_t i_base,
+                                                        uint32_t K, uint32_t nchunks) {
+    const uint32_t c = blockIdx.x % ncols;
+    const uint32_t slot = blockIdx.x / ncols, per8 = (nchunks + 7) / 8;
+    const uint32_t chunk = K > 1 ? (slot % 8) * per8 + slot / 8 : slot;
+    if (chunk >= nchunks) return;
+    const uint64_t i0 = i_base + (uint64_t)chunk * K;
+    const uint32_t t = threadIdx.x, l = t & 63;
+    uint64_t heads;
+    {
+        const uint64_t i = i0 + l;
+        bool head = false;
+        if (l < K && i < n) {
+            const uint64_t v = idx[i];
+            head = v < nrec && (i == 0 || (idx[i - 1] >> 8) != (v >> 8));
+        }
+        heads = __builtin_amdgcn_ballot_w64(head);
+    }
+    const uint32_t w = t >> 6;                  // bit positions 64 w .. 64 w + 63: words 2 w, 2 w + 1 of the column
+    const uint2* recs2 = reinterpret_cast<const uint2*>(recs);
+    while (heads) {
+        const uint32_t u = (uint32_t)__builtin_ctzll(heads);
+        heads &= heads - 1;
+        uint64_t i = i0 + u;
+        const uint64_t S = idx[i] >> 8;
+        uint4* row = &dbs[((S * ncols + c) * 256 + t) * 2];
+        const uint4 a = row[0], b = row[1];
+        uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        for (;;) {
+            // Entries i .. i + 63, one per lane: how many continue the run,
+            // and this wave's two words of each of their records.
+            const uint64_t il = i + l;
+            uint64_t v = ~0ull;
+            if (il < n) v = idx[il];
+            const bool in = v < nrec && (v >> 8) == S;
+            uint2 wv = make_uint2(0, 0);
+            if (in) wv = recs2[(il * ncols + c) * 4 + w];
+            const uint64_t m = __builtin_amdgcn_ballot_w64(in);
+            const uint32_t cnt = ~m ? (uint32_t)__builtin_ctzll(~m) : 64u;
+            const uint32_t lo = (uint32_t)v & 255u;
+            const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)lo, 0);
+            // (entries of one run share S: consecutive records <=> consecutive low bytes)
+            const bool seq = cnt >= kUpdSeqMin && __builtin_amdgcn_ballot_w64(l < cnt && lo != off + l) == 0;
+            if (seq) {
+                uint64_t M = 0;              // bit q: bit t of the column of update q's record
+#pragma unroll
+                for (uint32_t bb = 0; bb < 32; ++bb) {
+                    const uint64_t m0 = __builtin_amdgcn_ballot_w64(((wv.x >> bb) & 1u) != 0);
+                    const uint64_t m1 = __builtin_amdgcn_ballot_w64(((wv.y >> bb) & 1u) != 0);
+                    M = l == bb ? m0 : M;
+                    M = l == bb + 32 ? m1 : M;
+                }
+                const uint64_t V = cnt == 64 ? ~0ull : (1ull << cnt) - 1;       // updates of the batch
+                // Update q is bit off + q of the row's 256: word gg takes bits [sh, sh + 32) of M.
+                auto win = [](uint64_t mm, int sh) -> uint32_t {
+                    return sh >= 64 || sh <= -32 ? 0u : sh >= 0 ? (uint32_t)(mm >> sh) : (uint32_t)mm << -sh;
+                };
+#pragma unroll
+                for (int gg = 0; gg < 8; ++gg) {
+                    const int sh = 32 * gg - (int)off;
+                    const uint32_t mk = win(V, sh);                                    // scalar
+                    x[gg] = (x[gg] & ~mk) | (win(M, sh) & mk);
+                }
+            }
+            for (uint32_t q = 0; !seq && q < cnt; ++q) {
+                const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)q);
+                const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)wv.x, (int)q);
+                const uint32_t w1 = (uint32_t)__builtin_amdgcn_readlane((int)wv.y, (int)q);
+                const uint32_t g = r >> 5, j = r & 31;
+                const uint32_t nb = 0u - (((l < 32 ? w0 : w1) >> (l & 31)) & 1u);     // all ones / all zeros
+#pragma unroll
+                for (uint32_t gg = 0; gg < 8; ++gg) {
+                    const uint32_t mk = g == gg ? 1u << j : 0u;                        // scalar
+                    x[gg] = (x[gg] & ~mk) | (nb & mk);
+                }
+            }
+            if (cnt < 64) break;
+            i += 64;
+        }
+        row[0] = make_uint4(x[0], x[1], x[2], x[3]);
+        row[1] = make_uint4(x[4], x[5], x[6], x[7]);
+    }
+}
+
+// Record idx[i] of the sliced DB in row-major form (zeros for idx[i] >= nrec):
+// one thread per output word (i, c, wd), bit b of it = bit j of
+// dbs[S][c][32 wd + b][g].  Not a hot path: 32 loads of 4 bytes per word.
+__global__ __launch_bounds__(256) void k_gather_sliced(const uint32_t* __restrict__ dbs, uint64_t nrec, uint32_t ncols,
+                                                        const uint64_t* __restrict__ idx, uint64_t nwords,
+                                                        uint32_t* __restrict__ out) {
+    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (tid >= nwords) return;
+    const uint32_t wd = (uint32_t)(tid & 7);
+    const uint64_t ic = tid >> 3;
+    const uint32_t c = (uint32_t)(ic % ncols);
+    const uint64_t r = idx[ic / ncols];
+    uint32_t o = 0;
+    if (r < nrec) {
+        const uint64_t S = r >> 8;
+        const uint32_t g = ((uint32_t)r & 255u) >> 5, j = (uint32_t)r & 31u;
+        const uint32_t* p = dbs + ((S * ncols + c) * 256 + 32 * wd) * 8 + g;
+#pragma unroll 8
+        for (uint32_t b = 0; b < 32; ++b) o |= ((p[8 * b] >> j) & 1u) << b;
+    }
+    out[tid] = o;
+}
+
+// The same two operations on a row-major DB [nrec][rec_bytes] (a handle kept
+// row-major): one thread per 16 bytes.  The scatter takes sorted indices and
+// writes only the last update of equal ones; indices >= nrec are skipped
+// (gather: read as zeros).
+__global__ __launch_bounds__(256) void k_scatter_rows(uint4* __restrict__ db, uint64_t nrec, uint32_t q16,
+                                                       const uint64_t* __restrict__ idx, const uint4* __restrict__ recs,
+                                                       uint64_t n, uint64_t npieces) {
+    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (tid >= npieces) return;
+    const uint64_t i = tid / q16;
+    const uint64_t r = idx[i];
+    if (r >= nrec || (i + 1 < n && idx[i + 1] == r)) return;
+    db[r * q16 + tid % q16] = recs[tid];
+}
+
+__global__ __launch_bounds__(256) void k_gather_rows(const uint4* __restrict__ db, uint64_t nrec, uint32_t q16,
+                                                      const uint64_t* __restrict__ idx, uint64_t npieces,
+                                                      uint4* __restrict__ out) {
+    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (tid >= npieces) return;
+    const uint64_t r = idx[tid / q16];
+    out[tid] = r < nrec ? db[r * q16 + tid % q16] : make_uint4(0, 0, 0, 0);
+}
+
+static bool rec_bytes_ok(uint64_t rec_bytes) {
+    return rec_bytes != 0 && rec_bytes % 32 == 0 && rec_bytes <= kFoldMaxRecBytes;
+}
+
+hipError_t launch_update_sliced(uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx,
+                                const uint8_t* recs, uint64_t n, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    if (n == 0 || nrec == 0) return hipSuccess;
+    const uint64_t C = rec_bytes / 32, nsg = (nrec + 255) / 256;
+    // n updates over nsg super-groups: runs of n / nsg updates at least on
+    // average, so chunks of that many hold about one head or fewer each.
+    uint32_t K = 1;
+    while (K < 64 && 2ull * K <= n / nsg) K *= 2;
+    // One workgroup per (chunk, column), in launches of at most 2^30
+    // (chunks rounded up to a multiple of 8: the kernel's slot -> chunk map).
+    const uint64_t per = ((1ull << 30) / C - 8) * K;    // updates per launch
+    for (uint64_t i0 = 0; i0 < n; i0 += per) {
+        const uint64_t m = n - i0 < per ? n - i0 : per;
+        const uint64_t nchunks = (m + K - 1) / K;
+        hipLaunchKernelGGL(k_update_sliced, dim3((uint32_t)((nchunks + 7) / 8 * 8 * C)), dim3(256), 0, st,
+                           reinterpret_cast<uint4*>(dbs), nrec, (uint32_t)C, idx,
+                           reinterpret_cast<const uint32_t*>(recs), n, i0, K, (uint32_t)nchunks);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// n records of per_rec threads each, in launches of at most 2^30 workgroups
+// of 256 threads over whole records: fn(first record, records, threads).
+template <class F>
+static hipError_t for_record_chunks(uint64_t n, uint64_t per_rec, F fn) {
+    const uint64_t per = (1ull << 38) / per_rec;         // records per launch: <= 2^38 threads
+    for (uint64_t i0 = 0; i0 < n; i0 += per) {
+        const uint64_t m = n - i0 < per ? n - i0 : per;
+        fn(i0, m, m * per_rec);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_gather_sliced(const uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
+                                uint8_t* out, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    const uint64_t C = rec_bytes / 32;
+    return for_record_chunks(n, 8 * C, [&](uint64_t i0, uint64_t, uint64_t threads) {
+        hipLaunchKernelGGL(k_gather_sliced, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const uint32_t*>(dbs), nrec, (uint32_t)C, idx + i0, threads,
+                           reinterpret_cast<uint32_t*>(out + i0 * rec_bytes));
+    });
+}
+
+hipError_t launch_update_rows(uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, const uint8_t* recs,
+                              uint64_t n, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    const uint64_t q16 = rec_bytes / 16;
+    return for_record_chunks(n, q16, [&](uint64_t i0, uint64_t, uint64_t threads) {
+        // n - i0: the look-ahead idx[i + 1] of a chunk's last record reads the next chunk's first index.
+        hipLaunchKernelGGL(k_scatter_rows, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<uint4*>(db), nrec, (uint32_t)q16, idx + i0,
+                           reinterpret_cast<const uint4*>(recs + i0 * rec_bytes), n - i0, threads);
+    });
+}
+
+hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
+                              uint8_t* out, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    const uint64_t q16 = rec_bytes / 16;
+    return for_record_chunks(n, q16, [&](uint64_t i0, uint64_t, uint64_t threads) {
+        hipLaunchKernelGGL(k_gather_rows, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const uint4*>(db), nrec, (uint32_t)q16, idx + i0, threads,
+                           reinterpret_cast<uint4*>(out + i0 * rec_bytes));
+    });
+}
+
 namespace {
 // The DB pieces of a matrix-core fold over at least this many DB bytes are
 // loaded nontemporal.  r05 (tools/archive/r05_nt.sh, profiles/r05/fold_nt/, B = 64,

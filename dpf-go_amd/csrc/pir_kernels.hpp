@@ -45,6 +45,24 @@ hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes,
 hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
                                   uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st);
 
+// Records of a resident DB changed and read back in place (k_update_sliced,
+// k_gather_sliced).  Update: record idx[i] := recs[i * rec_bytes ..) for
+// i < n, idx non-decreasing (of equal indices the last wins; unsorted input
+// leaves the touched super-groups unspecified but stays inside the buffers),
+// idx[i] >= nrec skipped; afterwards dbs is what launch_slice_db writes from
+// the modified row-major DB.  Gather: out[i] = record idx[i] in row-major
+// form, any order, zeros for idx[i] >= nrec.  No workspace, asynchronous on
+// st.  idx 8-byte, dbs / recs / out 16-byte aligned.  The _rows forms do the
+// same on a row-major DB [nrec][rec_bytes].
+hipError_t launch_update_sliced(uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx,
+                                const uint8_t* recs, uint64_t n, hipStream_t st);
+hipError_t launch_gather_sliced(const uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
+                                uint8_t* out, hipStream_t st);
+hipError_t launch_update_rows(uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, const uint8_t* recs,
+                              uint64_t n, hipStream_t st);
+hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
+                              uint8_t* out, hipStream_t st);
+
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per
 // matrix-core fold workgroup (0 = the default and maximum, 2^15 = 2^23

@@ -105,8 +105,13 @@ SIGNATURES = {
     "dpf_xor_fold_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_answer_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_answer_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_db_update_sliced_wide_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
+    "dpf_pir_db_gather_sliced_wide_dev": (_int, [_int, _vp, _u64, _sz, _vp, _sz, _vp, _vp]),
     "dpf_pir_db_create_wide": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_rec_bytes": (_sz, [_vp]),
+    "dpf_pir_db_nrec": (_u64, [_vp]),
+    "dpf_pir_db_update": (_int, [_vp, _u64p, _u8p, _sz]),
+    "dpf_pir_db_read": (_int, [_vp, _u64p, _sz, _u8p]),
     "dpf_pir_db_create": (_int, [_u8p, _u64, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_answer": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_pir_db_free": (None, [_vp]),
@@ -570,6 +575,21 @@ def pir_answer_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_db, nrec
                                          nrec, rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
 
 
+def pir_db_update_sliced_wide_dev(d_dbs, nrec: int, rec_bytes: int, d_idx, d_recs, n: int, device: int = 0,
+                                  stream=None) -> None:
+    """Set record d_idx[i] (uint64, non-decreasing; last of equal ones wins,
+    >= nrec skipped) of the wide bit-sliced DB to d_recs[i], in place."""
+    _check(lib().dpf_pir_db_update_sliced_wide_dev(device, _ptr(d_dbs), nrec, rec_bytes, _ptr(d_idx), _ptr(d_recs), n,
+                                                   _stream_handle(stream)))
+
+
+def pir_db_gather_sliced_wide_dev(d_dbs, nrec: int, rec_bytes: int, d_idx, n: int, d_out, device: int = 0,
+                                  stream=None) -> None:
+    """d_out[i] = record d_idx[i] (any order; zeros for >= nrec) of the wide bit-sliced DB, row-major."""
+    _check(lib().dpf_pir_db_gather_sliced_wide_dev(device, _ptr(d_dbs), nrec, rec_bytes, _ptr(d_idx), n, _ptr(d_out),
+                                                   _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -590,13 +610,20 @@ class PirDB:
             raise ValueError("DB size must be a multiple of %d bytes" % rec_bytes)
         self.logN = logN
         self.rec_bytes = rec_bytes
-        self.nrec = d.size // rec_bytes
+        nrec = d.size // rec_bytes
         h = _vp()
         if rec_bytes == 32:
-            _check(lib().dpf_pir_db_create(_buf(d), self.nrec, logN, ngpus, ctypes.byref(h)))
+            _check(lib().dpf_pir_db_create(_buf(d), nrec, logN, ngpus, ctypes.byref(h)))
         else:
-            _check(lib().dpf_pir_db_create_wide(_buf(d), self.nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
+            _check(lib().dpf_pir_db_create_wide(_buf(d), nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
         self._h = h
+
+    @property
+    def nrec(self) -> int:
+        """Records the handle holds, asked of the handle (dpf_pir_db_nrec).
+        Read-only, and 0 once the handle is closed: it used to be a plain
+        attribute that kept the count given to the constructor."""
+        return int(lib().dpf_pir_db_nrec(self._h))
 
     def answer(self, keys: np.ndarray) -> np.ndarray:
         kk = np.ascontiguousarray(keys, dtype=np.uint8)
@@ -604,6 +631,23 @@ class PirDB:
         ans = np.zeros((n, int(lib().dpf_pir_db_rec_bytes(self._h))), np.uint8)
         _check(lib().dpf_pir_answer(self._h, _buf(kk), kl, n, _buf(ans)))
         return ans
+
+    def update(self, idx, recs) -> None:
+        """Record idx[i] := recs[i] in place (any order; of repeated indices
+        the last wins).  One index >= nrec raises DPFPanic (DPF_ERR_PARAM)
+        and changes nothing."""
+        ix = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        r = np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1)
+        if r.size != ix.size * self.rec_bytes:
+            raise ValueError("recs must hold len(idx) records of %d bytes" % self.rec_bytes)
+        _check(lib().dpf_pir_db_update(self._h, ix.ctypes.data_as(_u64p), _buf(r), ix.size))
+
+    def read(self, idx) -> np.ndarray:
+        """The records idx[i] as the DB now holds them, (len(idx), rec_bytes), in the caller's order."""
+        ix = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros((ix.size, self.rec_bytes), np.uint8)
+        _check(lib().dpf_pir_db_read(self._h, ix.ctypes.data_as(_u64p), ix.size, _buf(out)))
+        return out
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -192,6 +192,35 @@ func (p *PirDB) Answer(keys []DPFkey) [][]byte {
 	return out
 }
 
+// NRec is the number of records the database was created with (dpf_pir_db_nrec).
+func (p *PirDB) NRec() uint64 {
+	return uint64(C.dpf_pir_db_nrec(p.h))
+}
+
+// Update sets record idx[i] to recs[i*RecBytes():(i+1)*RecBytes()] on the
+// GPUs, in place (dpf_pir_db_update).  idx may be in any order; of repeated
+// indices the last wins.  An index >= NRec() panics and changes nothing.
+func (p *PirDB) Update(idx []uint64, recs []byte) {
+	if len(recs) != len(idx)*p.RecBytes() {
+		panic("dpf: recs must hold len(idx) records")
+	}
+	if len(idx) == 0 {
+		return
+	}
+	check(C.dpf_pir_db_update(p.h, (*C.uint64_t)(unsafe.Pointer(&idx[0])), u8(recs), C.size_t(len(idx))))
+}
+
+// Read returns the records idx[i] as the database now holds them, RecBytes()
+// bytes each, in the caller's order (dpf_pir_db_read).
+func (p *PirDB) Read(idx []uint64) []byte {
+	out := make([]byte, len(idx)*p.RecBytes())
+	if len(idx) == 0 {
+		return out
+	}
+	check(C.dpf_pir_db_read(p.h, (*C.uint64_t)(unsafe.Pointer(&idx[0])), C.size_t(len(idx)), u8(out)))
+	return out
+}
+
 // Close frees the GPU copies of the database.
 func (p *PirDB) Close() {
 	if p.h != nil {

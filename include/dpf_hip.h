@@ -308,6 +308,29 @@ int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t key
 int dpf_pir_answer_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
                             uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
                             uint8_t* d_ans, void* d_work, void* stream);
+/* Records of a sliced DB changed and read back in place, without re-slicing
+ * it.  Both are asynchronous on `stream`, need no workspace and synchronise
+ * nothing; rec_bytes as above (32 is the C = 1 case of the same kernels);
+ * d_dbs, d_recs and d_out 16-byte and d_idx 8-byte aligned, none of them
+ * null (else DPF_ERR_PARAM, checked before any device call); n == 0 returns
+ * DPF_OK without a launch.
+ * dpf_pir_db_update_sliced_wide_dev sets record d_idx[i] of d_dbs to
+ * d_recs[i * rec_bytes ..) for every i < n.  d_idx must be non-decreasing; of
+ * equal indices the last one wins; entries with d_idx[i] >= nrec are skipped
+ * (so the padding of the last super-group stays zero: "records past nrec
+ * read as 0").  Afterwards d_dbs holds, byte for byte, what
+ * dpf_pir_db_slice_wide_dev writes from the modified row-major DB.  With
+ * indices that are not sorted the content of the touched super-groups is
+ * unspecified, but no access leaves the buffers.  One workgroup rewrites
+ * each touched 8-KiB tile (super-group, column) alone: no atomics, and
+ * untouched tiles are neither read nor written.
+ * dpf_pir_db_gather_sliced_wide_dev writes d_out[i * rec_bytes ..) = record
+ * d_idx[i] in row-major form, indices in any order, zeros for
+ * d_idx[i] >= nrec. */
+int dpf_pir_db_update_sliced_wide_dev(int device, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                      const uint64_t* d_idx, const uint8_t* d_recs, size_t n, void* stream);
+int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                      const uint64_t* d_idx, size_t n, uint8_t* d_out, void* stream);
 /* Tuning / test limits of the XOR fold launches (process-wide; 0 = default):
  * at most max_blocks workgroups per fold launch (default and maximum 1024),
  * and at most max_sg_per_block super-groups of 256 records per matrix-core
@@ -354,6 +377,22 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t key_len, size_t nke
 int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
                            void** handle);
 size_t dpf_pir_db_rec_bytes(void* handle);
+/* Records the handle was created with (0 for NULL). */
+uint64_t dpf_pir_db_nrec(void* handle);
+/* Change / read back n records of a resident DB in place: record idx[i] :=
+ * recs[i * rec_bytes ..), resp. out[i * rec_bytes ..) := record idx[i].  idx
+ * may be in any order and may repeat; of repeated indices the last update
+ * wins, and a read returns the records in the caller's order.  Every index
+ * is checked against dpf_pir_db_nrec first: one index >= nrec returns
+ * DPF_ERR_PARAM and nothing is changed (a DB does not grow).  The host sorts
+ * the updates (stably), splits them by shard and sends each shard's part
+ * through a staging buffer in chunks of at most 256 MiB of records; a chunk
+ * runs on its device's stream under that device's mutex, so a concurrent
+ * dpf_pir_answer sees the DB wholly before or wholly after each chunk.
+ * Sliced shards take dpf_pir_db_update_sliced_wide_dev, row-major ones
+ * (DPF_PIR_FOLD=lds) a plain scatter.  Synchronous. */
+int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, size_t n);
+int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out);
 void dpf_pir_db_free(void* handle);
 
 #ifdef __cplusplus
