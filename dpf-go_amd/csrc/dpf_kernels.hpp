@@ -64,7 +64,17 @@ uint32_t eval_frontier_level(uint32_t stop, uint64_t pts_per_key);
 // Batched Eval kernel choice: 1 = visited-node trie below the frontier.
 int set_eval_trie(int on);   // returns the previous choice
 int get_eval_trie();
-bool eval_trie_built();   // k_eval_trie is in this build (the experimental one)
+// The trie kernel itself (k_eval_trie) is in eval_trie.hip, which only the
+// experimental library links; the product library links
+// experimental_none.cpp instead: not built, never ok, the launcher refuses.
+// launch_eval takes it where eval_trie_ok() (one key per workgroup, <= 1024
+// points per key, frontier level L): the queries of nkeys keys from the
+// frontier (fseed, ft) computed by launch_eval.
+bool eval_trie_built();
+bool eval_trie_ok(uint32_t stop, uint32_t logN, uint64_t pts_per_key, uint32_t L);
+hipError_t launch_eval_trie(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nkeys,
+                            uint64_t pts_per_key, const uint4* fseed, const uint8_t* ft, uint32_t L, uint8_t* out,
+                            hipStream_t st);
 uint64_t eval_frontier_bytes(uint64_t nkeys, uint32_t stop, uint64_t pts_per_key);
 hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nq,
                        uint64_t pts_per_key, uint8_t* out, void* frontier, uint64_t frontier_bytes,

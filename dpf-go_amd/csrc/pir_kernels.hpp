@@ -73,9 +73,11 @@ void set_fold_limits(uint32_t max_blocks, uint32_t max_sg);
 // from their expanded records (launch_unpack) and the matrix-core fold over
 // the sliced DB in one launch; where pir_fused_ok() (<= 64 keys, 2^8 .. 2^10
 // blocks of 256 leaf pairs in the subtree; any_size: from one block, for
-// tests).  Same ans / parts contract.  Built only with DPF_PIR_FUSED_KERNEL=1
-// (make experimental): measured slower than the two launches;
-// otherwise pir_fused_ok() is false and the launcher refuses.
+// tests).  Same ans / parts contract.  Defined in pir_fused.hip, which only
+// the experimental library links (make experimental): measured slower than
+// the two launches.  The product library links
+// experimental_none.cpp instead: pir_fused_ok() is false and the launcher
+// refuses.
 bool pir_fused_ok(uint64_t nkeys, uint32_t stop, uint32_t prefix_bits, bool any_size = false);
 // Whether k_pir_fused is compiled into this library (the experimental build only).
 bool pir_fused_built();

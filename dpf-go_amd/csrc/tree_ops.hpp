@@ -1,6 +1,6 @@
 // tree_ops.hpp — device building blocks of the GGM tree walks shared by the
-// tree / Eval kernels (dpf_kernels.hip) and the fused PIR kernel
-// (pir_kernels.hip): nodes, correction words, the PRG step and the leaf
+// tree / Eval kernels (dpf_kernels.hip, eval_trie.hip) and the fused PIR
+// kernel (pir_fused.hip): nodes, correction words, the PRG step and the leaf
 // conversion.  Reference: dpf/dpf.go:46-69 (getT/clr/prg), :171-241 (Eval,
 // evalFullRecursive) and the key layout :89-92,111-112,137-138,165-167.
 #pragma once
@@ -24,6 +24,12 @@ __device__ __forceinline__ uint32_t tmask(uint32_t t) { return t != 0 ? 0xffffff
 // Eval's path bit with Go's shift semantics (dpf.go:194: a shift of 64 or
 // more gives 0, so logN > 63 keys go left on their top logN-64 levels).
 __device__ __forceinline__ uint32_t path_bit(uint64_t x, uint32_t s) { return s < 64 ? (uint32_t)(x >> s) & 1u : 0u; }
+// Eval's result: bit x & 127 of the query's leaf block.
+__device__ __forceinline__ uint8_t eval_bit(Blk o, uint64_t x) {
+    const uint32_t b = (uint32_t)(x & 127);
+    const uint32_t w = (b >> 5) == 0 ? o.c0 : (b >> 5) == 1 ? o.c1 : (b >> 5) == 2 ? o.c2 : o.c3;
+    return (uint8_t)((w >> (b & 31)) & 1u);
+}
 
 // Expanded key record (words): [0..3] root seed, [4] root t, [8+8l..] level l
 // {sCW[4], tLCW, tRCW, 0, 0}, [8+8*stop..+3] final CW.

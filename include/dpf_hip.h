@@ -350,8 +350,9 @@ int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block);
  * never reach HBM; measured slower on MI355X, the split
  * path elsewhere.  DPF_PIR_FUSED_ANY fuses any slice from logN -
  * prefix_bits = 16 (test mode).  Answers are identical.  The fused kernel is
- * built only in the experimental library (make -C dpf-go_amd experimental):
- * the product library returns DPF_ERR_PARAM for DPF_PIR_FUSED and
+ * linked only into the experimental library (make -C dpf-go_amd
+ * experimental: the product library's objects plus csrc/pir_fused.hip and
+ * csrc/eval_trie.hip): the product library returns DPF_ERR_PARAM for DPF_PIR_FUSED and
  * DPF_PIR_FUSED_ANY.  Process-wide; env DPF_PIR_KERNEL=split|fused|fused-any. */
 #define DPF_PIR_SPLIT 0
 #define DPF_PIR_FUSED 1

@@ -49,6 +49,57 @@ def test_library_is_gfx950_code_object():
     assert b"gfx950" in blob
 
 
+PRODUCT_LIB = os.path.join(ROOT, "dpf-go_amd", "lib", "libdpf_hip.so")
+EXP_LIB = os.path.join(ROOT, "dpf-go_amd", "lib", "variants", "libdpf_hip_exp.so")
+
+
+def test_product_library_refuses_the_experimental_kernels():
+    """The product library links experimental_none.cpp in the place of the
+    trie Eval and fused PIR kernels: selecting either is DPF_ERR_PARAM, the
+    message names the build that has them, and the selection stays where it
+    was.  Settings only: no call here touches a device."""
+    import ctypes
+    L = ctypes.CDLL(PRODUCT_LIB)
+    L.dpf_last_error.restype = ctypes.c_char_p
+    L.dpf_pir_kernel_for.argtypes = [ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32]
+    for call, arg in ((L.dpf_set_pir_kernel, dpf.PIR_FUSED), (L.dpf_set_pir_kernel, dpf.PIR_FUSED_ANY),
+                      (L.dpf_set_eval_kernel, dpf.EVAL_TRIE)):
+        assert call(arg) == dpf.DPF_ERR_PARAM
+        assert "make -C dpf-go_amd experimental" in L.dpf_last_error().decode()
+    assert L.dpf_get_pir_kernel() == dpf.PIR_SPLIT
+    assert L.dpf_get_eval_kernel() == dpf.EVAL_WALK
+    assert L.dpf_pir_kernel_for(64, 24, 0) == dpf.PIR_SPLIT
+
+
+def _kernel_handles(lib_path):
+    """Demangled names of the kernels a library holds: its kernel handles,
+    the data symbols that carry a kernel's signature."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", "-C", lib_path], capture_output=True, text=True, check=True)
+    rows = (ln.split(None, 2) for ln in out.stdout.splitlines())
+    return {r[2] for r in rows if len(r) == 3 and r[1] in "BDV" and "(" in r[2]}
+
+
+def test_experimental_library_is_the_product_plus_two_kernels():
+    """`make experimental` links the product library's own objects with
+    pir_fused.o and eval_trie.o in the place of experimental_none.o, and
+    compiles nothing else: the two libraries' kernels differ by exactly
+    k_pir_fused<true>, k_pir_fused<false> and k_eval_trie."""
+    import shutil
+    import subprocess
+    pkg = os.path.join(ROOT, "dpf-go_amd")
+    if not (os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    subprocess.run(["make", "-s", "-j4", "-C", pkg, "experimental"], check=True, capture_output=True, text=True)
+    product, exp = _kernel_handles(PRODUCT_LIB), _kernel_handles(EXP_LIB)
+    assert len(product) >= 90
+    assert not [k for k in product if "k_pir_fused" in k or "k_eval_trie" in k]
+    assert product <= exp
+    extra = sorted(k.split("(")[0] for k in exp - product)
+    assert extra == ["dpfk::k_eval_trie", "void dpfk::k_pir_fused<false>", "void dpfk::k_pir_fused<true>"]
+    assert sorted(os.listdir(os.path.join(pkg, "lib", "variants", "exp"))) == ["eval_trie.o", "pir_fused.o"]
+
+
 def test_sizes():
     for logN in (0, 3, 6, 7, 8, 20, 32, 63):
         stop = max(logN - 7, 0)

@@ -173,8 +173,9 @@ def _trie_built() -> bool:
 
 @pytest.fixture()
 def trie_kernel():
-    """The trie kernel is in the experimental build only (make -C dpf-go_amd
-    experimental; DPF_LIB=dpf-go_amd/lib/variants/libdpf_hip_exp.so)."""
+    """The trie kernel (csrc/eval_trie.hip) is linked into the experimental
+    library only (make -C dpf-go_amd experimental;
+    DPF_LIB=dpf-go_amd/lib/variants/libdpf_hip_exp.so)."""
     if not _trie_built():
         with pytest.raises(dpf.DPFPanic):
             dpf.set_eval_kernel("trie")

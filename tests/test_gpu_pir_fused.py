@@ -3,10 +3,10 @@ product path: tree kernel, then the matrix-core fold) and of the fused PIR
 kernel (k_pir_fused: subtree EvalFull and the matrix-core fold in one launch,
 DESIGN.md §4.4) against the CPU oracle's XOR inner product over EvalFull bits
 (dpf/dpf.go:213-262 for the bits), and the 2-server property at the configs[4]
-shape (logN=24, 2^24 x 32 B DB).  The fused kernel is in the experimental
-build only (make -C dpf-go_amd experimental; run these tests with
-DPF_LIB=dpf-go_amd/lib/variants/libdpf_hip_exp.so): with the product library
-its legs are skipped."""
+shape (logN=24, 2^24 x 32 B DB).  The fused kernel (csrc/pir_fused.hip) is
+linked into the experimental library only (make -C dpf-go_amd experimental;
+run these tests with DPF_LIB=dpf-go_amd/lib/variants/libdpf_hip_exp.so): with
+the product library its legs are skipped."""
 import numpy as np
 import pytest
 

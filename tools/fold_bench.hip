@@ -4,6 +4,7 @@
 // answers against a plain host fold.  Args: [nkeys] [rec_bytes] [log2 nrec].
 // Build with -DFOLD_SRC=<file> to A/B another revision (tools/ab/).  One
 // JSON line.
+// Build (from tools/): hipcc --offload-arch=gfx950 -O3 -std=c++17 fold_bench.hip -o fold_bench
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

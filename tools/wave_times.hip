@@ -7,6 +7,9 @@
 // wave finished its root-to-subtree walk (the serial, latency-bound part of a
 // small launch).  Prints one JSON line; per-wave rows go to the file named by
 // WAVE_TIMES_CSV when set.
+// Build (from tools/; experimental_none.cpp: launch_eval's trie calls):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 wave_times.hip \
+//       ../dpf-go_amd/csrc/experimental_none.cpp -o wave_times
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
