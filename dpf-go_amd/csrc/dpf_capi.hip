@@ -5,18 +5,21 @@
 // device-resident (_dev) entry points only enqueue on the caller's stream.
 // There is no CPU evaluation path: without a usable gfx950 device every
 // evaluation call fails with DPF_ERR_NODEV.
+//
+// What needs no device lives in host-only headers with CPU tests of their
+// own: stage_plan.hpp cuts a host-buffer call into the chunks of the staging
+// pipeline (chunk sizes, subtree slabs, output offsets), copy_pool.hpp is the
+// thread pool of the pinned <-> caller-buffer copies, pir_update_plan.hpp
+// plans dpf_pir_db_update / _read.  This file keeps the HIP calls: buffers,
+// streams, events and launches, and the argument checks of the entry points.
 #include <hip/hip_runtime.h>
-#include <sched.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <unordered_map>
@@ -27,12 +30,16 @@
 #include "../../include/dpf_hip.h"
 #include "dpf_internal.hpp"
 #include "bs_kernels.hpp"
+#include "copy_pool.hpp"
 #include "dpf_kernels.hpp"
 #include "pir_kernels.hpp"
 #include "pir_update_plan.hpp"
+#include "stage_plan.hpp"
 
+using dpfh::CopyPool;
 using dpfh::full_len;
 using dpfh::key_len;
+using dpfh::kStageBytes;
 using dpfh::stop_of;
 
 namespace {
@@ -50,44 +57,27 @@ int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(DPF_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
-struct DevBuf {
+// A buffer grown on demand: device memory (hipMalloc), or with Pinned a
+// pinned host staging buffer (hipHostMalloc).
+template <bool Pinned>
+struct Buf {
     void* p = nullptr;
     size_t cap = 0;
     hipError_t ensure(size_t n) {
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, n);
+        release();
+        hipError_t e = Pinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
         if (e == hipSuccess) cap = n;
         return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
         p = nullptr;
         cap = 0;
     }
 };
-
-// Pinned host staging buffer (hipHostMalloc), grown on demand.
-struct HostBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>;
 
 struct Dev {
     int id = 0;
@@ -99,138 +89,6 @@ struct Dev {
     DevBuf keys, work, out, xs;
     HostBuf pin[2];
     ~Dev();
-};
-
-// Parallel host memcpy for the pinned -> caller-buffer leg of the pipelined
-// copies (one thread reaches ~10 GB/s; PCIe delivers ~50).  A fixed pool of
-// workers takes 2 MiB pieces; the caller works too and waits for the rest.
-class CopyPool {
-   public:
-    static CopyPool& get() {
-        static CopyPool pool;
-        return pool;
-    }
-    // memcpy over the pool in 2 MiB pieces.
-    void memcpy_par(void* dst, const void* src, size_t n) {
-        if (n <= kPiece || workers_.empty()) {
-            memcpy(dst, src, n);
-            return;
-        }
-        struct Ctx {
-            uint8_t* d;
-            const uint8_t* s;
-            size_t n;
-        } c{static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), n};
-        parallel_for((n + kPiece - 1) / kPiece, &c, [](void* p, size_t i) {
-            const Ctx& x = *static_cast<const Ctx*>(p);
-            const size_t off = i * kPiece;
-            memcpy(x.d + off, x.s + off, std::min(kPiece, x.n - off));
-        });
-    }
-    // First touch of a (fresh) destination, one write per 4 KiB page, so the
-    // page faults -- one per 2 MiB with transparent huge pages -- are taken
-    // by all workers at once instead of inside the timed copies.
-    void prefault_par(void* dst, size_t n) {
-        struct Ctx {
-            volatile uint8_t* d;
-            size_t n;
-        } c{static_cast<volatile uint8_t*>(dst), n};
-        parallel_for((n + kPiece - 1) / kPiece, &c, [](void* p, size_t i) {
-            const Ctx& x = *static_cast<const Ctx*>(p);
-            const size_t off = i * kPiece, end = std::min(off + kPiece, x.n);
-            for (size_t o = off; o < end; o += 4096) x.d[o] = 0;
-        });
-    }
-
-   private:
-    static constexpr size_t kPiece = (size_t)2 << 20;
-    struct Job {
-        void (*fn)(void*, size_t);
-        void* ctx;
-        size_t npieces;
-        size_t active = 0;   // workers inside run(); guarded by mu_
-        std::atomic<size_t> next{0}, done{0};
-        Job(void (*f)(void*, size_t), void* c, size_t np) : fn(f), ctx(c), npieces(np) {}
-    };
-    // fn(ctx, i) for i < npieces over the caller and the workers.
-    void parallel_for(size_t npieces, void* ctx, void (*fn)(void*, size_t)) {
-        Job job{fn, ctx, npieces};
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            jobs_.push_back(&job);
-        }
-        cv_.notify_all();
-        run(job);
-        // Workers that picked the job leave it (active == 0) before it goes out of scope.
-        std::unique_lock<std::mutex> lk(mu_);
-        done_cv_.wait(lk, [&] { return job.done.load() == job.npieces && job.active == 0; });
-        jobs_.erase(std::find(jobs_.begin(), jobs_.end(), &job));
-    }
-    // Run pieces of `job` until none is left.
-    static void run(Job& job) {
-        for (size_t i; (i = job.next.fetch_add(1)) < job.npieces;) {
-            job.fn(job.ctx, i);
-            job.done.fetch_add(1);
-        }
-    }
-    // One worker per CPU this process may use (affinity mask, capped by a
-    // cgroup CPU quota), minus the caller, at most 31: first-touch page
-    // faults of a fresh caller buffer and the copy itself both scale with
-    // threads (one thread copies ~10 GB/s; PCIe delivers ~50).
-    CopyPool() {
-        const unsigned n = std::min(31u, usable_cpus() > 1 ? usable_cpus() - 1 : 0u);
-        for (unsigned i = 0; i < n; ++i) workers_.emplace_back([this] { loop(); });
-    }
-    static unsigned usable_cpus() {
-        unsigned n = std::thread::hardware_concurrency();
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) n = (unsigned)CPU_COUNT(&set);
-        if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char q[32] = {0};
-            unsigned long per = 0;
-            if (fscanf(f, "%31s %lu", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) {
-                const unsigned long quota = strtoul(q, nullptr, 10) / per;
-                if (quota >= 1 && quota < n) n = (unsigned)quota;
-            }
-            fclose(f);
-        }
-        return n > 0 ? n : 1;
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : workers_) t.join();
-    }
-    void loop() {
-        std::unique_lock<std::mutex> lk(mu_);
-        for (;;) {
-            // Take the job the predicate found, under the same lock hold: the
-            // piece counter (`next`) moves without the lock, so a second
-            // pending() call could find the job already exhausted.
-            Job* j = nullptr;
-            cv_.wait(lk, [&] { return stop_ || (j = pending()) != nullptr; });
-            if (stop_) return;
-            ++j->active;
-            lk.unlock();
-            run(*j);
-            lk.lock();
-            --j->active;
-            done_cv_.notify_all();
-        }
-    }
-    Job* pending() {
-        for (Job* j : jobs_)
-            if (j->next.load() < j->npieces) return j;
-        return nullptr;
-    }
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    std::vector<Job*> jobs_;
-    std::vector<std::thread> workers_;
-    bool stop_ = false;
 };
 
 // Open devices.  Entry points take a snapshot (shared_ptr copies) under
@@ -303,11 +161,14 @@ int check_gfx950(int ordinal) {
     return DPF_OK;
 }
 
-// Open exactly the HIP ordinals `ids` (caller holds g_mu, registry empty).
-int open_list(const std::vector<int>& ids) {
+// Open exactly the HIP ordinals `ids`, or with no ids the first `ngpus`
+// visible devices (all if ngpus <= 0).  Caller holds g_mu, registry empty.
+int open_list(std::vector<int> ids, int ngpus = 0) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0) return fail(DPF_ERR_NODEV, "dpf: no HIP device visible (gfx950 required)");
+    if (ids.empty())
+        for (int i = 0; i < (ngpus > 0 ? std::min(n, ngpus) : n); ++i) ids.push_back(i);
     for (int id : ids) {
         if (id < 0 || id >= n) return fail(DPF_ERR_PARAM, "dpf: device ordinal out of range");
         if (int rc = check_gfx950(id)) return rc;
@@ -329,13 +190,7 @@ int open_list(const std::vector<int>& ids) {
 int open_devices(int ngpus) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_devs.empty()) return (int)g_devs.size();
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) return fail(DPF_ERR_NODEV, "dpf: no HIP device visible (gfx950 required)");
-    if (ngpus > 0) n = std::min(n, ngpus);
-    std::vector<int> ids;
-    for (int i = 0; i < n; ++i) ids.push_back(i);
-    return open_list(ids);
+    return open_list({}, ngpus);
 }
 
 // The opened devices, opening every visible one on first use.  Returns an
@@ -401,6 +256,14 @@ TreeWs tree_ws(void* work, size_t nk, uint32_t stop) {
     return w;
 }
 
+// Expanded keys at the start of a PIR or batched-Eval workspace, padded to 256 B.
+size_t pir_ek_bytes(size_t nkeys, uint32_t logN) { return align256(nkeys * dpfk::ek_words(stop_of(logN)) * 4); }
+
+// Batched-Eval workspace: expanded keys (256-B padded), then the frontier.
+size_t eval_work_bytes(size_t nkeys, size_t ppk, uint32_t logN) {
+    return pir_ek_bytes(nkeys, logN) + dpfk::eval_frontier_bytes(nkeys, stop_of(logN), ppk);
+}
+
 // The back end a call uses, decided once per call (expansion and launches agree).
 bool want_bs() { return g_aes_impl.load(std::memory_order_relaxed) == DPF_AES_BITSLICED; }
 
@@ -422,31 +285,52 @@ hipError_t run_tree(const TreeWs& w, size_t k0, size_t n, uint32_t stop, uint32_
     return dpfk::launch_evalfull(w.ek + k0 * dpfk::ek_words(stop), n, stop, prefix_bits, prefix, out, stride, st);
 }
 
-// One-shot tree pass from the key bytes in HBM: straight from the bytes when
-// the T-table back end runs a wave-uniform shape (dpfk::evalfull_raw_ok: no
-// unpack launch, d_work untouched), else expand into d_work and run.
-hipError_t tree_from_keys(const uint8_t* d_keys, size_t klen, size_t nk, uint32_t stop, uint32_t prefix_bits,
-                          uint64_t prefix, uint8_t* out, uint64_t stride, void* d_work, hipStream_t st, bool bs,
-                          bool* expanded) {
-    if (!bs && dpfk::evalfull_raw_ok(nk, stop, prefix_bits)) {
-        *expanded = false;
-        return dpfk::launch_evalfull_raw(d_keys, klen, nk, stop, prefix_bits, prefix, out, stride, st);
-    }
-    *expanded = true;
-    const TreeWs w = tree_ws(d_work, nk, stop);
-    hipError_t e = expand_keys(d_keys, klen, nk, stop, w, st, bs);
-    return e != hipSuccess ? e : run_tree(w, 0, nk, stop, prefix_bits, prefix, out, stride, st, bs);
+// The expanded form's layout depends on (nkeys, stop) (tree_ws), so each
+// expanded workspace is recorded here and dpf_evalfull_expanded_dev refuses
+// one expanded for another shape instead of reading misplaced records.
+std::mutex g_exp_mu;
+// Also records whether the byte-sliced planes were built: the T-table back
+// end expands only its own records, and switching to the byte-sliced one
+// later derives them from those (launch_bs_from_ek) on first use.
+struct Expanded {
+    size_t nkeys;
+    uint32_t stop;
+    bool bs;
+};
+std::unordered_map<const void*, Expanded>& g_expanded = *new std::unordered_map<const void*, Expanded>();
+
+// Every entry point that expands keys into a caller's d_work records what it
+// left there (the same tree_ws layout), so a later dpf_evalfull_expanded_dev
+// never reads planes built from other keys; dpf_eval_batch_dev's workspace
+// has another layout past the records and is dropped.
+void note_expanded(const void* d_work, size_t nkeys, uint32_t stop, bool bs) {
+    std::lock_guard<std::mutex> lk(g_exp_mu);
+    g_expanded[d_work] = {nkeys, stop, bs};
+}
+void forget_expanded(const void* d_work) {
+    std::lock_guard<std::mutex> lk(g_exp_mu);
+    g_expanded.erase(d_work);
 }
 
-// Pipelined device -> host output of `nchunks` chunks (<= chunk_cap bytes
-// each).  produce(i, dbuf, bytes, host_off) enqueues the kernels writing
-// chunk i into device slot dbuf on d.st.  Kernel i, the PCIe copy of chunk
-// i-1 (d.cst, into a pinned slot) and the host copy of chunk i-2 (pinned ->
-// caller buffer, CopyPool) overlap; two device and two pinned slots.
-constexpr size_t kStageBytes = (size_t)32 << 20;
-constexpr size_t kSlabMinOut = (size_t)8 << 20;    // one key's output from which it is cut into >= 4 slabs
+// One-shot tree pass from the key bytes in HBM, with a caller's d_work:
+// straight from the bytes when the T-table back end runs a wave-uniform shape
+// (dpfk::evalfull_raw_ok: no unpack launch, d_work untouched and its record
+// dropped), else expand into d_work, run, and record what d_work now holds.
+hipError_t tree_from_keys(const uint8_t* d_keys, size_t klen, size_t nk, uint32_t stop, uint32_t prefix_bits,
+                          uint64_t prefix, uint8_t* out, uint64_t stride, void* d_work, hipStream_t st, bool bs) {
+    forget_expanded(d_work);
+    if (!bs && dpfk::evalfull_raw_ok(nk, stop, prefix_bits))
+        return dpfk::launch_evalfull_raw(d_keys, klen, nk, stop, prefix_bits, prefix, out, stride, st);
+    const TreeWs w = tree_ws(d_work, nk, stop);
+    hipError_t e = expand_keys(d_keys, klen, nk, stop, w, st, bs);
+    if (e == hipSuccess) e = run_tree(w, 0, nk, stop, prefix_bits, prefix, out, stride, st, bs);
+    if (e == hipSuccess) note_expanded(d_work, nk, stop, bs);
+    return e;
+}
 
-int ensure_staging(Dev& d, size_t chunk_cap) {
+// Staging of the pipelined host-buffer paths: two device slots of chunk_cap
+// bytes in d.out, two pinned slots of pin_off + chunk_cap bytes.
+int ensure_staging(Dev& d, size_t chunk_cap, size_t pin_off) {
     if (!d.cst) {
         HIP_TRY(hipStreamCreateWithFlags(&d.cst, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
@@ -454,8 +338,8 @@ int ensure_staging(Dev& d, size_t chunk_cap) {
             HIP_TRY(hipEventCreateWithFlags(&d.ev_c[i], hipEventDisableTiming));
         }
     }
-    HIP_TRY(hipError_t(d.out.ensure(2 * chunk_cap)));
-    for (int i = 0; i < 2; ++i) HIP_TRY(d.pin[i].ensure(chunk_cap));
+    HIP_TRY(d.out.ensure(2 * chunk_cap));
+    for (int i = 0; i < 2; ++i) HIP_TRY(d.pin[i].ensure(pin_off + chunk_cap));
     return DPF_OK;
 }
 
@@ -480,18 +364,25 @@ void hint_hugepages(uint8_t* p, size_t n) {
     if (e > a) (void)madvise((void*)a, e - a, MADV_HUGEPAGE);
 }
 
+// Pipelined device -> host output of `nchunks` chunks (<= chunk_cap bytes
+// each; the plans of stage_plan.hpp).  produce(i, dbuf, bytes, host_off)
+// enqueues the kernels writing chunk i into device slot dbuf on d.st.  Kernel
+// i, the PCIe copy of chunk i-1 (d.cst, into a pinned slot) and the host copy
+// of chunk i-2 (pinned -> caller buffer, CopyPool) overlap; two device and two
+// pinned slots.  Chunk i lands at out + off_i - out_base; [out, out +
+// out_bytes) is the whole destination.  Results sit pin_off bytes into a
+// pinned slot: the bytes before them are produce's (batched Eval's points).
 template <class Produce>
 int pipeline_d2h(Dev& d, size_t nchunks, size_t chunk_cap, Produce produce, uint8_t* out, size_t out_bytes,
-                 size_t out_base = 0) {
-    // Chunk i lands at out + off_i - out_base; [out, out + out_bytes) is the whole destination.
+                 size_t out_base = 0, size_t pin_off = 0) {
     if (nchunks == 0) return DPF_OK;
     hint_hugepages(out, out_bytes);
-    if (int rc = ensure_staging(d, chunk_cap)) return rc;
+    if (int rc = ensure_staging(d, chunk_cap, pin_off)) return rc;
     size_t bytes[2] = {0, 0}, off[2] = {0, 0};
     auto drain = [&](size_t i) -> int {              // chunk i: wait for its PCIe copy, then host copy
         const int s = (int)(i & 1);
         HIP_TRY(hipEventSynchronize(d.ev_c[s]));
-        CopyPool::get().memcpy_par(out + (off[s] - out_base), d.pin[s].p, bytes[s]);
+        CopyPool::get().memcpy_par(out + (off[s] - out_base), (uint8_t*)d.pin[s].p + pin_off, bytes[s]);
         return DPF_OK;
     };
     for (size_t i = 0; i < nchunks; ++i) {
@@ -501,7 +392,7 @@ int pipeline_d2h(Dev& d, size_t nchunks, size_t chunk_cap, Produce produce, uint
         if (int rc = produce(i, dbuf, bytes[s], off[s])) return rc;
         HIP_TRY(hipEventRecord(d.ev_k[s], d.st));
         HIP_TRY(hipStreamWaitEvent(d.cst, d.ev_k[s], 0));
-        HIP_TRY(hipMemcpyAsync(d.pin[s].p, dbuf, bytes[s], hipMemcpyDeviceToHost, d.cst));
+        HIP_TRY(hipMemcpyAsync((uint8_t*)d.pin[s].p + pin_off, dbuf, bytes[s], hipMemcpyDeviceToHost, d.cst));
         HIP_TRY(hipEventRecord(d.ev_c[s], d.cst));
         if (i == std::min<size_t>(1, nchunks - 1) && out_bytes >= ((size_t)64 << 20) && prefault_output())
             CopyPool::get().prefault_par(out, out_bytes);   // while the GPU works on chunks 0-1
@@ -511,78 +402,57 @@ int pipeline_d2h(Dev& d, size_t nchunks, size_t chunk_cap, Produce produce, uint
     return drain(nchunks - 1);
 }
 
-// Host-buffer EvalFull of keys [0, nk) on one device.  Chunks are groups of
-// whole keys, or subtree slabs of one key when its output exceeds a chunk.
-int full_on_device(Dev& d, const uint8_t* keys, size_t klen, size_t nk, uint32_t logN, uint8_t* out) {
+// Host-buffer EvalFull of one device's plan (dpfh::full_plan: groups of whole
+// keys or subtree slabs; dpfh::split_plan: this device's subtree of one key)
+// into the caller's whole buffer `out`.  Every chunk runs straight from the
+// key bytes when each launch shape of the plan allows it (dpfk::
+// evalfull_raw_ok), else the keys are expanded once for all chunks.
+int full_on_device(Dev& d, const uint8_t* keys, size_t klen, uint32_t logN, const dpfh::FullPlan& plan, uint8_t* out) {
     std::lock_guard<std::mutex> lk(d.mu);
     DeviceGuard g(d.id);
     const uint32_t stop = stop_of(logN);
-    const size_t olen = full_len(logN);
-    const size_t per = olen <= kStageBytes ? kStageBytes / olen : 1;   // keys per chunk
-    HIP_TRY(hipError_t(d.keys.ensure(nk * klen)));
-    HIP_TRY(hipError_t(d.work.ensure(tree_ws_bytes(nk, stop, 0, std::min(per, nk)))));
+    const size_t nk = plan.nk;
+    HIP_TRY(d.keys.ensure(nk * klen));
+    HIP_TRY(d.work.ensure(tree_ws_bytes(nk, stop, plan.split_bits, std::min(plan.per, nk))));
     HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nk * klen, hipMemcpyHostToDevice, d.st));
     const TreeWs w = tree_ws(d.work.p, nk, stop);
     const bool bs = want_bs();
     const uint8_t* dk = (const uint8_t*)d.keys.p;
-    uint32_t pb = 0;                                      // one key's output exceeds a chunk: subtree slabs
-    while ((olen >> pb) > kStageBytes) ++pb;
-    // A key whose output is >= kSlabMinOut goes in >= 4 subtree slabs even
-    // when it fits one chunk, so its kernel, PCIe copy and host copy overlap
-    // (BenchmarkEvalFull's logN = 28 is one 32 MiB key: as one chunk, the
-    // three ran back to back).
-    if (olen >= kSlabMinOut && pb < 2) pb = 2;
-    // Every chunk straight from the key bytes when each chunk shape allows it
-    // (tree_from_keys), else the keys are expanded once for all chunks.
-    const bool raw = !bs && (pb == 0 ? dpfk::evalfull_raw_ok(std::min(per, nk), stop, 0) &&
-                                                       (nk % per == 0 || dpfk::evalfull_raw_ok(nk % per, stop, 0))
-                                                 : dpfk::evalfull_raw_ok(1, stop, pb));
+    bool raw = !bs;
+    for (size_t i = 0; raw && i < plan.nshapes; ++i)
+        raw = dpfk::evalfull_raw_ok(plan.shape[i].nkeys, stop, plan.shape[i].prefix_bits);
     if (!raw) HIP_TRY(expand_keys(dk, klen, nk, stop, w, d.st, bs));
-    if (pb == 0) {
-        const size_t nch = (nk + per - 1) / per;
-        return pipeline_d2h(d, nch, std::min(per, nk) * olen, [&](size_t i, uint8_t* dbuf, size_t& bytes, size_t& off) {
-            const size_t k0 = i * per, n = std::min(per, nk - k0);
-            if (raw) HIP_TRY(dpfk::launch_evalfull_raw(dk + k0 * klen, klen, n, stop, 0, 0, dbuf, olen, d.st));
-            else HIP_TRY(run_tree(w, k0, n, stop, 0, 0, dbuf, olen, d.st, bs));
-            bytes = n * olen;
-            off = k0 * olen;
-            return DPF_OK;
-        }, out, nk * olen);
-    }
-    const size_t slab = olen >> pb, per_key = (size_t)1 << pb;
-    return pipeline_d2h(d, nk * per_key, slab, [&](size_t i, uint8_t* dbuf, size_t& bytes, size_t& off) {
-        const size_t k = i / per_key, p = i % per_key;
-        if (raw) HIP_TRY(dpfk::launch_evalfull_raw(dk + k * klen, klen, 1, stop, pb, p, dbuf, slab, d.st));
-        else HIP_TRY(run_tree(w, k, 1, stop, pb, p, dbuf, slab, d.st, bs));
-        bytes = slab;
-        off = k * olen + p * slab;
+    return pipeline_d2h(d, plan.nchunks, plan.cap, [&](size_t i, uint8_t* dbuf, size_t& bytes, size_t& off) {
+        const dpfh::FullChunk c = plan.chunk(i);
+        const uint64_t stride = plan.olen >> c.prefix_bits;   // one key's bytes of this subtree
+        if (raw)
+            HIP_TRY(dpfk::launch_evalfull_raw(dk + c.k0 * klen, klen, c.n, stop, c.prefix_bits, c.prefix, dbuf, stride,
+                                              d.st));
+        else
+            HIP_TRY(run_tree(w, c.k0, c.n, stop, c.prefix_bits, c.prefix, dbuf, stride, d.st, bs));
+        bytes = c.bytes;
+        off = c.off;
         return DPF_OK;
-    }, out, nk * olen);
+    }, out + plan.out_base, plan.out_bytes, plan.out_base);
 }
 
-size_t pir_ek_bytes(size_t nkeys, uint32_t logN);
-size_t eval_work_bytes(size_t nkeys, size_t ppk, uint32_t logN);
-
-// Host-buffer batched Eval on one device, pipelined over chunks of keys:
-// caller xs -> pinned (CopyPool) -> HBM (d.hst) -> the Eval kernels (d.st) -> pinned
-// (d.cst) -> caller out, two slots per stage, so chunk i's kernel overlaps
-// the PCIe copies of its neighbours.
+// Host-buffer batched Eval on one device, pipelined over chunks of keys
+// (dpfh::eval_plan): caller xs -> pinned (CopyPool) -> HBM (d.hst) -> the Eval
+// kernels (d.st) -> pinned (d.cst) -> caller out, two slots per stage, so
+// chunk i's kernel overlaps the PCIe copies of its neighbours.  A pinned slot
+// holds [xs qcap*8][results qcap].
 int eval_on_device(Dev& d, const uint8_t* keys, size_t klen, size_t nk, const uint64_t* xs, size_t ppk,
                    uint32_t logN, uint8_t* out) {
     std::lock_guard<std::mutex> lk(d.mu);
     DeviceGuard g(d.id);
     const uint32_t stop = stop_of(logN);
     const size_t ekw = dpfk::ek_words(stop);
-    const size_t per = std::max<size_t>(1, std::min(nk, kStageBytes / (ppk * 8)));   // keys per chunk
-    const size_t nch = (nk + per - 1) / per;
-    const size_t ekb = pir_ek_bytes(nk, logN);
-    const size_t fbytes = dpfk::eval_frontier_bytes(per, stop, ppk);
-    const size_t qcap = per * ppk;                        // queries per chunk
-    HIP_TRY(hipError_t(d.keys.ensure(std::max<size_t>(1, nk * klen))));
-    HIP_TRY(hipError_t(d.work.ensure(std::max<size_t>(16, ekb + fbytes))));
-    HIP_TRY(hipError_t(d.xs.ensure(2 * qcap * 8)));
-    if (int rc = ensure_staging(d, qcap)) return rc;      // d.out: 2 x qcap result bytes
-    for (int i = 0; i < 2; ++i) HIP_TRY(d.pin[i].ensure(qcap * 9));   // [xs qcap*8][results qcap]
+    const dpfh::EvalPlan plan = dpfh::eval_plan(nk, ppk);
+    const size_t qcap = plan.qcap, ekb = pir_ek_bytes(nk, logN);
+    const size_t fbytes = dpfk::eval_frontier_bytes(plan.per, stop, ppk);
+    HIP_TRY(d.keys.ensure(std::max<size_t>(1, nk * klen)));
+    HIP_TRY(d.work.ensure(std::max<size_t>(16, ekb + fbytes)));
+    HIP_TRY(d.xs.ensure(2 * qcap * 8));
     if (!d.hst) {
         HIP_TRY(hipStreamCreateWithFlags(&d.hst, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&d.ev_h[i], hipEventDisableTiming));
@@ -591,34 +461,20 @@ int eval_on_device(Dev& d, const uint8_t* keys, size_t klen, size_t nk, const ui
     HIP_TRY(dpfk::launch_unpack((const uint8_t*)d.keys.p, klen, nk, stop, (uint32_t*)d.work.p, d.st));
     const uint32_t* ek = (const uint32_t*)d.work.p;
     void* frontier = (uint8_t*)d.work.p + ekb;
-    auto drain = [&](size_t i) -> int {
+    return pipeline_d2h(d, plan.nchunks, qcap, [&](size_t i, uint8_t* dout, size_t& bytes, size_t& off) {
         const int s = (int)(i & 1);
-        const size_t k0 = i * per, q = std::min(per, nk - k0) * ppk;
-        HIP_TRY(hipEventSynchronize(d.ev_c[s]));
-        CopyPool::get().memcpy_par(out + k0 * ppk, (uint8_t*)d.pin[s].p + qcap * 8, q);
-        return DPF_OK;
-    };
-    for (size_t i = 0; i < nch; ++i) {
-        const int s = (int)(i & 1);
-        const size_t k0 = i * per, n = std::min(per, nk - k0), q = n * ppk;
-        uint8_t* pin = (uint8_t*)d.pin[s].p;
+        const size_t k0 = plan.k0(i), q = plan.n(i) * ppk;
         uint64_t* dxs = (uint64_t*)d.xs.p + (size_t)s * qcap;
-        uint8_t* dout = (uint8_t*)d.out.p + (size_t)s * qcap;
-        CopyPool::get().memcpy_par(pin, xs + k0 * ppk, q * 8);
+        CopyPool::get().memcpy_par(d.pin[s].p, xs + k0 * ppk, q * 8);
         if (i >= 2) HIP_TRY(hipStreamWaitEvent(d.hst, d.ev_k[s], 0));   // slot's previous kernel read its xs
-        HIP_TRY(hipMemcpyAsync(dxs, pin, q * 8, hipMemcpyHostToDevice, d.hst));
+        HIP_TRY(hipMemcpyAsync(dxs, d.pin[s].p, q * 8, hipMemcpyHostToDevice, d.hst));
         HIP_TRY(hipEventRecord(d.ev_h[s], d.hst));
         HIP_TRY(hipStreamWaitEvent(d.st, d.ev_h[s], 0));
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(d.st, d.ev_c[s], 0));    // slot's previous results copied out
         HIP_TRY(dpfk::launch_eval(ek + k0 * ekw, stop, logN, dxs, q, ppk, dout, frontier, fbytes, d.st));
-        HIP_TRY(hipEventRecord(d.ev_k[s], d.st));
-        HIP_TRY(hipStreamWaitEvent(d.cst, d.ev_k[s], 0));
-        HIP_TRY(hipMemcpyAsync(pin + qcap * 8, dout, q, hipMemcpyDeviceToHost, d.cst));
-        HIP_TRY(hipEventRecord(d.ev_c[s], d.cst));
-        if (i >= 1)
-            if (int rc = drain(i - 1)) return rc;
-    }
-    return drain(nch - 1);
+        bytes = q;
+        off = k0 * ppk;
+        return DPF_OK;
+    }, out, nk * ppk, 0, qcap * 8);
 }
 
 // Run fn(device_index, lo, hi) over `n` items split evenly across g devices.
@@ -648,43 +504,6 @@ DevList pick_devs(int ngpus, int* rc) {
     if (ngpus > 0 && (size_t)ngpus < devs.size()) devs.resize((size_t)ngpus);
     *rc = (int)devs.size();
     return devs;
-}
-
-// Expanded keys at the start of a PIR workspace, padded to 256 B.
-size_t pir_ek_bytes(size_t nkeys, uint32_t logN) {
-    return (nkeys * dpfk::ek_words(stop_of(logN)) * 4 + 255) & ~(size_t)255;
-}
-
-// Batched-Eval workspace: expanded keys (256-B padded), then the frontier.
-size_t eval_work_bytes(size_t nkeys, size_t ppk, uint32_t logN) {
-    return pir_ek_bytes(nkeys, logN) + dpfk::eval_frontier_bytes(nkeys, stop_of(logN), ppk);
-}
-
-// The expanded form's layout depends on (nkeys, stop) (tree_ws), so each
-// expanded workspace is recorded here and dpf_evalfull_expanded_dev refuses
-// one expanded for another shape instead of reading misplaced records.
-std::mutex g_exp_mu;
-// Also records whether the byte-sliced planes were built: the T-table back
-// end expands only its own records, and switching to the byte-sliced one
-// later derives them from those (launch_bs_from_ek) on first use.
-struct Expanded {
-    size_t nkeys;
-    uint32_t stop;
-    bool bs;
-};
-std::unordered_map<const void*, Expanded>& g_expanded = *new std::unordered_map<const void*, Expanded>();
-
-// Every entry point that expands keys into a caller's d_work records what it
-// left there (the same tree_ws layout), so a later dpf_evalfull_expanded_dev
-// never reads planes built from other keys; dpf_eval_batch_dev's workspace
-// has another layout past the records and is dropped.
-void note_expanded(const void* d_work, size_t nkeys, uint32_t stop, bool bs) {
-    std::lock_guard<std::mutex> lk(g_exp_mu);
-    g_expanded[d_work] = {nkeys, stop, bs};
-}
-void forget_expanded(const void* d_work) {
-    std::lock_guard<std::mutex> lk(g_exp_mu);
-    g_expanded.erase(d_work);
 }
 
 }  // namespace
@@ -795,7 +614,8 @@ int dpf_evalfull_batch(const uint8_t* keys, size_t klen, size_t nkeys, uint32_t 
     if (g <= 0) return g;
     const size_t olen = full_len(logN);
     return shard(nkeys, g, [&](int dev, size_t lo, size_t hi) {
-        return full_on_device(*devs[(size_t)dev], keys + lo * klen, klen, hi - lo, logN, out + lo * olen);
+        return full_on_device(*devs[(size_t)dev], keys + lo * klen, klen, logN, dpfh::full_plan(hi - lo, logN),
+                              out + lo * olen);
     });
 }
 
@@ -891,38 +711,14 @@ int dpf_evalfull_split(const uint8_t* key, size_t klen, uint32_t logN, uint8_t* 
     int have = 0;
     const DevList devs = pick_devs(0, &have);
     if (have <= 0) return have;
-    const uint32_t stop = stop_of(logN);
     const int want = ngpus <= 0 ? have : ngpus;
     if (want > have) return fail(DPF_ERR_PARAM, "dpf: more GPUs requested than opened");
     uint32_t pb = 0;
-    while ((1 << pb) < want) ++pb;
-    if ((1 << pb) != want || pb > stop) return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= 2^(logN-7)");
-    const size_t slab = full_len(logN) >> pb;
+    if (!dpfh::gpus_to_pb(want, stop_of(logN), &pb))
+        return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= 2^(logN-7)");
     return shard((size_t)want, want, [&](int dev, size_t lo, size_t hi) {
         (void)hi;
-        Dev& d = *devs[(size_t)dev];
-        std::lock_guard<std::mutex> lk(d.mu);
-        DeviceGuard gd(d.id);
-        HIP_TRY(hipError_t(d.keys.ensure(klen)));
-        HIP_TRY(hipError_t(d.work.ensure(tree_ws_bytes(1, stop, pb, 1))));
-        HIP_TRY(hipMemcpyAsync(d.keys.p, key, klen, hipMemcpyHostToDevice, d.st));
-        const TreeWs w = tree_ws(d.work.p, 1, stop);
-        const bool bs = want_bs();
-        const uint8_t* dk = (const uint8_t*)d.keys.p;
-        // This device's subtree (pb, lo), streamed out in sub-slabs (pb + extra, lo * 2^extra + j).
-        uint32_t extra = 0;
-        while ((slab >> extra) > kStageBytes && pb + extra < stop) ++extra;
-        const size_t sub = slab >> extra;
-        const bool raw = !bs && dpfk::evalfull_raw_ok(1, stop, pb + extra);
-        if (!raw) HIP_TRY(expand_keys(dk, klen, 1, stop, w, d.st, bs));
-        return pipeline_d2h(d, (size_t)1 << extra, sub, [&](size_t j, uint8_t* dbuf, size_t& bytes, size_t& off) {
-            const uint64_t p = ((uint64_t)lo << extra) + j;
-            if (raw) HIP_TRY(dpfk::launch_evalfull_raw(dk, klen, 1, stop, pb + extra, p, dbuf, sub, d.st));
-            else HIP_TRY(run_tree(w, 0, 1, stop, pb + extra, p, dbuf, sub, d.st, bs));
-            bytes = sub;
-            off = lo * slab + j * sub;
-            return DPF_OK;
-        }, out + lo * slab, slab, lo * slab);
+        return full_on_device(*devs[(size_t)dev], key, klen, logN, dpfh::split_plan(logN, pb, lo), out);
     });
 }
 
@@ -930,17 +726,12 @@ int dpf_evalfull_subtree_dev(int device, const uint8_t* d_keys, size_t klen, siz
                              uint32_t prefix_bits, uint64_t prefix, uint8_t* d_out, void* d_work, void* stream) {
     if (int rc = check_key(klen, logN)) return rc;
     const uint32_t stop = stop_of(logN);
-    if (prefix_bits > stop || (prefix_bits < 64 && (prefix >> prefix_bits) != 0))
-        return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
     if (nkeys == 0) return DPF_OK;
     DeviceGuard g(device);
     CuScope cus(stream);
-    const bool bs = want_bs();
-    bool expanded = false;
-    forget_expanded(d_work);
     HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, d_out, (uint64_t)16 << (stop - prefix_bits),
-                           d_work, (hipStream_t)stream, bs, &expanded));
-    if (expanded) note_expanded(d_work, nkeys, stop, bs);
+                           d_work, (hipStream_t)stream, want_bs()));
     return DPF_OK;
 }
 
@@ -999,7 +790,7 @@ int dpf_evalfull_expanded_dev(int device, void* d_work, size_t nkeys, uint32_t l
                               uint64_t prefix, uint8_t* d_out, void* stream) {
     if (logN > 63) return fail(DPF_ERR_PARAM, "dpf: logN > 63");
     const uint32_t stop = stop_of(logN);
-    if (prefix_bits > stop || (prefix >> prefix_bits) != 0) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
     if (nkeys == 0) return DPF_OK;
     const bool bs = want_bs();
     bool build_bs = false;
@@ -1074,14 +865,11 @@ int dpf_pir_kernel_for(size_t nkeys, uint32_t logN, uint32_t prefix_bits) {
                : DPF_PIR_SPLIT;
 }
 
-size_t dpf_pir_db_sliced_size(uint64_t nrec) { return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec, 32)); }
+// The 32-byte record forms are the _wide forms at rec_bytes = 32.
+size_t dpf_pir_db_sliced_size(uint64_t nrec) { return dpf_pir_db_sliced_size_wide(nrec, 32); }
 
 int dpf_pir_db_slice_dev(int device, const uint8_t* d_db, uint64_t nrec, uint8_t* d_dbs, void* stream) {
-    if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    DeviceGuard g(device);
-    HIP_TRY(dpfk::launch_slice_db(d_db, nrec, 32, d_dbs, (hipStream_t)stream));
-    return DPF_OK;
+    return dpf_pir_db_slice_wide_dev(device, d_db, nrec, 32, d_dbs, stream);
 }
 
 static int check_rec_bytes(size_t rec_bytes) {
@@ -1101,7 +889,7 @@ static int pir_answer(bool sliced, int device, const uint8_t* d_keys, size_t kle
     if (int rc = check_rec_bytes(rec_bytes)) return rc;
     if (int rc = check_key(klen, logN)) return rc;
     const uint32_t stop = stop_of(logN);
-    if (prefix_bits > stop || (prefix >> prefix_bits) != 0) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
     const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
     if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
     if (int rc = check_pir_bufs(d_keys, nkeys, d_db, nrec, d_ans, d_work)) return rc;
@@ -1130,10 +918,7 @@ static int pir_answer(bool sliced, int device, const uint8_t* d_keys, size_t kle
                                        parts, st));
         return DPF_OK;
     }
-    bool expanded = false;
-    forget_expanded(d_work);
-    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs, &expanded));
-    if (expanded) note_expanded(d_work, nkeys, stop, bs);
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, bs));
     HIP_TRY((sliced ? dpfk::launch_pir_fold_sliced : dpfk::launch_pir_fold)(
         (const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes, (uint32_t)nkeys, (uint32_t*)d_ans, parts, st));
     return DPF_OK;
@@ -1165,20 +950,47 @@ int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t kle
                       stream);
 }
 
-int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_dbs,
-                            uint64_t nrec, uint8_t* d_ans, void* d_work, void* stream) {
+// The three fold entries behind their rec_bytes check: the shape and buffer
+// checks in the order they report (bits_stride, nrec, alignment, null), then
+// the fold on the caller's stream -- sliced: the matrix-core fold over the
+// bit-sliced layout, else the LDS fold over the row-major payload.  d_work's
+// alignment is checked only for the wide sliced form above 32 bytes (work16).
+static int xor_fold(bool sliced, bool work16, int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                    const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
     if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
     if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
-    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0)
+    if (((uintptr_t)d_bits | (uintptr_t)d_db) % 16 != 0 || (uintptr_t)d_ans % 4 != 0 ||
+        (work16 && (uintptr_t)d_work % 16 != 0))
         return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
+    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_db))))
         return fail(DPF_ERR_PARAM, "dpf: null device buffer");
     DeviceGuard g(device);
     CuScope cus(stream);
     if (nkeys == 0) return DPF_OK;
-    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, 32, (uint32_t)nkeys,
-                                         (uint32_t*)d_ans, (uint32_t*)d_work, (hipStream_t)stream));
+    HIP_TRY((sliced ? dpfk::launch_pir_fold_sliced : dpfk::launch_pir_fold)(
+        (const uint32_t*)d_bits, bits_stride / 4, d_db, nrec, rec_bytes, (uint32_t)nkeys, (uint32_t*)d_ans,
+        (uint32_t*)d_work, (hipStream_t)stream));
     return DPF_OK;
+}
+
+int dpf_xor_fold_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_payload,
+                     uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
+    // Unlike check_rec_bytes, no DPF_PIR_MAX_REC_BYTES cap.
+    if (rec_bytes == 0 || rec_bytes % 32 != 0) return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 32");
+    return xor_fold(false, false, device, d_bits, bits_stride, nkeys, d_payload, nrec, rec_bytes, d_ans, d_work, stream);
+}
+
+int dpf_xor_fold_sliced_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_dbs,
+                            uint64_t nrec, uint8_t* d_ans, void* d_work, void* stream) {
+    return xor_fold(true, false, device, d_bits, bits_stride, nkeys, d_dbs, nrec, 32, d_ans, d_work, stream);
+}
+
+int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                 void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    return xor_fold(true, rec_bytes > 32, device, d_bits, bits_stride, nkeys, d_dbs, nrec, rec_bytes, d_ans, d_work,
+                    stream);
 }
 
 // ---- records of rec_bytes = 32 C bytes over the sliced layout -------------
@@ -1225,47 +1037,10 @@ int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t
     return DPF_OK;
 }
 
-int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
-                                 const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
-                                 void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
-    if (rec_bytes == 32) return dpf_xor_fold_sliced_dev(device, d_bits, bits_stride, nkeys, d_dbs, nrec, d_ans, d_work, stream);
-    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
-    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
-    if (((uintptr_t)d_bits | (uintptr_t)d_dbs) % 16 != 0 || (uintptr_t)d_ans % 4 != 0 || (uintptr_t)d_work % 16 != 0)
-        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_dbs))))
-        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    if (nkeys == 0) return DPF_OK;
-    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)d_bits, bits_stride / 4, d_dbs, nrec, rec_bytes,
-                                         (uint32_t)nkeys, (uint32_t*)d_ans, (uint32_t*)d_work, (hipStream_t)stream));
-    return DPF_OK;
-}
-
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
 
 int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
     dpfk::set_fold_limits(max_blocks, max_sg_per_block);
-    return DPF_OK;
-}
-
-int dpf_xor_fold_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_payload,
-                     uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
-    if (rec_bytes == 0 || rec_bytes % 32 != 0) return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 32");
-    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
-    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
-    if (((uintptr_t)d_bits | (uintptr_t)d_payload) % 16 != 0 || (uintptr_t)d_ans % 4 != 0)
-        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
-    if (nkeys > 0 && (!d_ans || !d_work || (nrec > 0 && (!d_bits || !d_payload))))
-        return fail(DPF_ERR_PARAM, "dpf: null device buffer");
-    DeviceGuard g(device);
-    CuScope cus(stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (nkeys == 0) return DPF_OK;
-    HIP_TRY(dpfk::launch_pir_fold((const uint32_t*)d_bits, bits_stride / 4, d_payload, nrec, rec_bytes, (uint32_t)nkeys,
-                                  (uint32_t*)d_ans, (uint32_t*)d_work, st));
     return DPF_OK;
 }
 
@@ -1307,8 +1082,7 @@ int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, u
     if (have <= 0) return have;
     const int want = ngpus <= 0 ? have : ngpus;
     uint32_t pb = 0;
-    while ((1 << pb) < want) ++pb;
-    if ((1 << pb) != want || want > have || pb > stop_of(logN))
+    if (want > have || !dpfh::gpus_to_pb(want, stop_of(logN), &pb))
         return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= opened devices and 2^(logN-7)");
     auto h = std::make_unique<PirDb>();
     h->logN = logN;
@@ -1374,9 +1148,9 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
         Dev& d = *h->devs[(size_t)dev];
         std::lock_guard<std::mutex> lk(d.mu);
         DeviceGuard gd(d.id);
-        HIP_TRY(hipError_t(d.keys.ensure(std::max<size_t>(1, nkeys * klen))));
-        HIP_TRY(hipError_t(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits))));
-        HIP_TRY(hipError_t(d.out.ensure(std::max<size_t>(32, nkeys * rb))));
+        HIP_TRY(d.keys.ensure(std::max<size_t>(1, nkeys * klen)));
+        HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+        HIP_TRY(d.out.ensure(std::max<size_t>(32, nkeys * rb)));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
         // (rec_bytes == 32: the _wide entries are the 32-byte entries.)
         int r = (h->sliced ? dpf_pir_answer_sliced_wide_dev : dpf_pir_answer_wide_dev)(
@@ -1422,8 +1196,8 @@ static int pir_update_chunk(PirDb* h, size_t s, const dpfh::PirUpdatePlan& plan,
     }
     std::lock_guard<std::mutex> lk(d.mu);
     DeviceGuard gd(d.id);
-    HIP_TRY(hipError_t(d.xs.ensure(m * 8)));
-    HIP_TRY(hipError_t(d.out.ensure(m * rb)));
+    HIP_TRY(d.xs.ensure(m * 8));
+    HIP_TRY(d.out.ensure(m * rb));
     const uint64_t* d_idx = (const uint64_t*)d.xs.p;
     HIP_TRY(hipMemcpyAsync(d.xs.p, plan.local.data() + a, m * 8, hipMemcpyHostToDevice, d.st));
     if (recs) {

@@ -12,7 +12,9 @@
  * EvalFull / Eval from several threads while another thread shuts the
  * library down and re-opens it, and frees a PIR handle after shutdown:
  * the CopyPool, shard() threads, per-device mutexes and the shared_ptr
- * device registry under the sanitizers.  Exit status 0 = pass.
+ * device registry under the sanitizers.  The CopyPool alone also has a CPU
+ * test, tests/c/copy_pool_test.cpp (ASan + UBSan, and ThreadSanitizer), and
+ * the chunk planning tests/c/stage_plan_test.cpp.  Exit status 0 = pass.
  */
 #include <pthread.h>
 #include <stdint.h>
