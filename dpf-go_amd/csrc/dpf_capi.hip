@@ -1037,6 +1037,83 @@ int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t
     return DPF_OK;
 }
 
+// Private writes (the dual of the fold): every argument is checked before
+// any device call, in the order rec_bytes, bits_stride, nrec, null, alignment.
+static int check_scatter_bufs(size_t rec_bytes, const void* d_bits, size_t bits_stride, uint64_t nrec,
+                              const void* d_msgs, const void* d_db) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
+    if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
+    if (!d_bits || !d_msgs || !d_db) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_bits | (uintptr_t)d_msgs | (uintptr_t)d_db) % 16 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    return DPF_OK;
+}
+
+static int xor_scatter(bool sliced, int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                       const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec, size_t rec_bytes, void* stream) {
+    if (int rc = check_scatter_bufs(rec_bytes, d_bits, bits_stride, nrec, d_msgs, d_db)) return rc;
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY((sliced ? dpfk::launch_scatter_sliced : dpfk::launch_scatter_rows)(
+        (const uint32_t*)d_bits, bits_stride / 4, d_db, nrec, rec_bytes, d_msgs, nkeys, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_xor_scatter_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_msgs,
+                        uint8_t* d_db, uint64_t nrec, size_t rec_bytes, void* stream) {
+    return xor_scatter(false, device, d_bits, bits_stride, nkeys, d_msgs, d_db, nrec, rec_bytes, stream);
+}
+
+int dpf_xor_scatter_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                    const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                    void* stream) {
+    return xor_scatter(true, device, d_bits, bits_stride, nkeys, d_msgs, d_dbs, nrec, rec_bytes, stream);
+}
+
+// The private write of the two *_dev entries below: the subtree EvalFull into
+// the workspace (pir_answer's layout, always the split path), then the
+// scatter of the messages over the DB.
+static int pir_write(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                     uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec,
+                     size_t rec_bytes, void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (int rc = check_key(klen, logN)) return rc;
+    const uint32_t stop = stop_of(logN);
+    if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
+    if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
+    if (!d_keys || !d_msgs || !d_db || !d_work) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_msgs | (uintptr_t)d_db | (uintptr_t)d_work) % 16 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    // [tree workspace | selection bits = EvalFull bytes of the subtree | (the fold's partials: unused)]
+    uint8_t* bits = (uint8_t*)d_work + align256(tree_ws_bytes(nkeys, stop, prefix_bits, nkeys));
+    const uint64_t per_key = (uint64_t)16 << (stop - prefix_bits);
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, prefix_bits, prefix, bits, per_key, d_work, st, want_bs()));
+    HIP_TRY((sliced ? dpfk::launch_scatter_sliced : dpfk::launch_scatter_rows)(
+        (const uint32_t*)bits, per_key / 4, d_db, nrec, rec_bytes, d_msgs, nkeys, st));
+    return DPF_OK;
+}
+
+int dpf_pir_write_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                           uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec,
+                           size_t rec_bytes, void* d_work, void* stream) {
+    return pir_write(false, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_msgs, d_db, nrec, rec_bytes, d_work,
+                     stream);
+}
+
+int dpf_pir_write_sliced_wide_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                                  uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_dbs,
+                                  uint64_t nrec, size_t rec_bytes, void* d_work, void* stream) {
+    return pir_write(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_msgs, d_dbs, nrec, rec_bytes, d_work,
+                     stream);
+}
+
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
 
 int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
@@ -1242,6 +1319,38 @@ int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, si
 
 int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out) {
     return pir_update_or_read(handle, idx, n, nullptr, out);
+}
+
+// Every shard applies the batch to its slice: keys and messages up through
+// the device's staging buffers, tree and scatter on the device's stream under
+// its mutex, and the call returns when the stream is idle, so a concurrent
+// dpf_pir_answer sees a shard before or after the whole batch.
+int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, const uint8_t* msgs) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (int rc = check_key(klen, h->logN)) return rc;
+    if (nkeys == 0) return DPF_OK;
+    if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    const int g = (int)h->shard.size();
+    const size_t rb = h->rec_bytes;
+    return shard((size_t)g, g, [&](int dev, size_t lo, size_t hi) {
+        (void)hi;
+        if (h->shard_n[lo] == 0) return (int)DPF_OK;
+        Dev& d = *h->devs[(size_t)dev];
+        std::lock_guard<std::mutex> lk(d.mu);
+        DeviceGuard gd(d.id);
+        HIP_TRY(d.keys.ensure(nkeys * klen));
+        HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+        HIP_TRY(d.out.ensure(nkeys * rb));
+        HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
+        HIP_TRY(hipMemcpyAsync(d.out.p, msgs, nkeys * rb, hipMemcpyHostToDevice, d.st));
+        int r = (h->sliced ? dpf_pir_write_sliced_wide_dev : dpf_pir_write_wide_dev)(
+            d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)d.out.p,
+            (uint8_t*)h->shard[lo], h->shard_n[lo], rb, d.work.p, d.st);
+        if (r) return r;
+        HIP_TRY(hipStreamSynchronize(d.st));
+        return (int)DPF_OK;
+    });
 }
 
 void dpf_pir_db_free(void* handle) { delete (PirDb*)handle; }

@@ -31,6 +31,7 @@
 //                  looked up by up to 4 x 64 keys (lane = key): 2
 //                  ds_read_b128 per key per group instead of 32 masked XORs.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
@@ -38,6 +39,7 @@
 #include "dpf_kernels.hpp"
 #include "fold_ops.hpp"
 #include "pir_kernels.hpp"
+#include "pir_scatter_plan.hpp"
 
 namespace dpfk {
 
@@ -1177,6 +1179,229 @@ hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_byt
                            reinterpret_cast<const uint4*>(db), nrec, (uint32_t)q16, idx + i0, threads,
                            reinterpret_cast<uint4*>(out + i0 * rec_bytes));
     });
+}
+
+// ---- private writes: messages XORed into the records the bits select ------
+// The dual of the fold: db[i] ^= XOR over keys k with bit i of bits[k] set of
+// msgs[k].  In the sliced layout the 32 records of a word dbs[S][c][n][g] are
+// the 32 selection bits of word 8 S + g of a key's row, so
+//   dbs[S][c][n][g] ^= XOR over k with bit 256 c + n of msgs[k] set of bits[k][8 S + g]
+// with no bit transposition anywhere: one v_bitop3 (acc ^ (mask & sel)) per
+// (key, word), the mask a sign-extended message bit (one v_bfe_i32 per four
+// words).
+//
+// k_scatter_sliced<CG>: a workgroup takes a run of super-groups [s0, s1) of a
+// group of up to CG columns and one tile of kt <= 64 keys (the plan:
+// pir_scatter_plan.hpp).  Tile (S, c) is 512 uint4; thread t owns uint4 t and
+// t + 256 of it: words g = 4 h .. 4 h + 3 (h = t & 1) of bit positions
+// n = t >> 1 and 128 + (t >> 1), so a wave's loads and stores are contiguous
+// KiBs and a thread needs only half of a key's 8 selection words per
+// super-group: one broadcast ds_read_b128 per key (two per key, with a thread
+// per bit position, put the LDS pipe level with the VALU at one column).  Its
+// message bits -- bit k of mb[ci][slot] = bit 256 (c0 + ci) + n of key k's
+// message -- are read once per run, from the messages staged in LDS.  The
+// selection words of kScatterSB super-groups at a time are staged in LDS by
+// coalesced 16-byte loads (a key's 128 contiguous bytes by 8 lanes), masked
+// there to the records below nrec: whatever the caller left in the bits past
+// nrec, the padding of the last super-group stays zero.  Words past the end of
+// a key's row (wpk) are not read.  The next tile's loads are issued before the
+// current one's arithmetic.  Each tile is read once and written once by one
+// workgroup: no atomics, no scratch.
+constexpr int kScatterSB = 4;                        // super-groups per staging round
+constexpr int kScatterKT = (int)dpfh::kScatterKeyTile;
+static_assert(dpfh::kScatterMaxCols == 4, "k_scatter_sliced is instantiated for 1 .. 4 columns");
+static_assert(dpfh::kScatterMaxBlocks == kFoldMaxBlocks && dpfh::kScatterMaxSg == kFoldMaxSgPerBlock,
+              "the scatter plan's defaults are set_fold_limits' defaults");
+
+// The bits of selection word ww (records 32 ww ..) that are records below nrec.
+__device__ __forceinline__ uint32_t scatter_live(uint64_t ww, uint64_t nrec) {
+    const uint64_t r0 = ww * 32;
+    return nrec >= r0 + 32 ? ~0u : nrec <= r0 ? 0u : (1u << (uint32_t)(nrec - r0)) - 1u;
+}
+
+template <int CG>
+__global__ __launch_bounds__(256) void k_scatter_sliced(const uint32_t* __restrict__ bits, uint64_t wpk,
+                                                        uint4* __restrict__ dbs, uint64_t nrec, uint64_t nsg,
+                                                        uint32_t ncols, const uint4* __restrict__ msgs, uint32_t rec_u4,
+                                                        uint32_t kt, uint64_t run, uint32_t ncg, uint64_t u0) {
+    __shared__ uint4 sel[kScatterKT][kScatterSB][2];            // 8 KiB; first the messages [kt][2 CG]
+    static_assert(sizeof(sel) >= (size_t)kScatterKT * 2 * CG * sizeof(uint4), "the staged messages fit");
+    const uint32_t t = threadIdx.x, h = t & 1, n = t >> 1;
+    const uint64_t u = u0 + blockIdx.x;
+    const uint64_t r = u / ncg;
+    const uint32_t c0 = (uint32_t)(u % ncg) * CG;
+    const uint64_t s0 = r * run, s1 = s0 + run < nsg ? s0 + run : nsg;
+    if (s0 >= s1) return;                                      // (uniform; the plan launches no such workgroup)
+
+    // Message bits of this thread's two bit positions, per column.
+    uint32_t mb[CG][2][2];                                     // [column][slot][key word]
+    {
+        uint4* mst = &sel[0][0][0];
+        for (uint32_t i = t; i < kt * 2 * CG; i += 256) {
+            const uint32_t k = i / (2 * CG), q = 2 * c0 + i % (2 * CG);
+            mst[i] = q < 2 * ncols ? msgs[(uint64_t)k * rec_u4 + q] : make_uint4(0, 0, 0, 0);
+        }
+        __syncthreads();
+        const uint8_t* mbytes = reinterpret_cast<const uint8_t*>(mst);
+#pragma unroll
+        for (int ci = 0; ci < CG; ++ci)
+#pragma unroll
+            for (int sl = 0; sl < 2; ++sl) {
+                const uint32_t nn = n + 128 * sl;
+                uint32_t lo = 0, hi = 0;
+                for (uint32_t k = 0; k < kt; ++k) {
+                    const uint32_t b = (mbytes[k * 32 * CG + 32 * ci + (nn >> 3)] >> (nn & 7)) & 1u;
+                    lo |= k < 32 ? b << k : 0u;
+                    hi |= k >= 32 ? b << (k - 32) : 0u;
+                }
+                mb[ci][sl][0] = lo;
+                mb[ci][sl][1] = hi;
+            }
+    }
+
+    auto tile = [&](uint64_t S, int ci) { return &dbs[((S * ncols + c0 + ci) * 256) * 2 + t]; };
+    auto load = [&](uint64_t S, uint4 (&x)[CG][2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ci = 0; ci < CG; ++ci)
+            if (c0 + ci < ncols) {
+                x[ci][0] = tile(S, ci)[0];
+                x[ci][1] = tile(S, ci)[256];
+            }
+    };
+    uint4 cur[CG][2] = {}, nxt[CG][2] = {};
+    load(s0, cur);
+    for (uint64_t S0 = s0; S0 < s1; S0 += kScatterSB) {
+        __syncthreads();                                       // the previous round's (or the messages') reads are done
+#pragma unroll
+        for (uint32_t i = t; i < (uint32_t)kScatterKT * kScatterSB * 2; i += 256) {
+            const uint32_t k = i / (2 * kScatterSB), s = (i / 2) % kScatterSB, hh = i & 1;
+            const uint64_t ww = 8 * (S0 + s) + 4 * hh;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (k < kt && S0 + s < s1 && ww < wpk) {           // wpk is a multiple of 4: the whole uint4 is in the row
+                v = *reinterpret_cast<const uint4*>(bits + (uint64_t)k * wpk + ww);
+                v.x &= scatter_live(ww, nrec);
+                v.y &= scatter_live(ww + 1, nrec);
+                v.z &= scatter_live(ww + 2, nrec);
+                v.w &= scatter_live(ww + 3, nrec);
+            }
+            sel[k][s][hh] = v;
+        }
+        __syncthreads();
+        for (uint32_t s = 0; s < (uint32_t)kScatterSB && S0 + s < s1; ++s) {
+            const uint64_t S = S0 + s;
+            if (S + 1 < s1) load(S + 1, nxt);
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                if (kt <= 32u * w) break;
+                const uint32_t kend = kt - 32u * w < 32u ? kt - 32u * w : 32u;
+                for (uint32_t kk = 0; kk < kend; kk += 8) {    // keys past kt: zero message bits, zero words
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) {
+                        const uint4 sv = sel[32 * w + kk + j][s][h];
+#pragma unroll
+                        for (int ci = 0; ci < CG; ++ci)
+#pragma unroll
+                            for (int sl = 0; sl < 2; ++sl) {
+                                const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)mb[ci][sl][w], kk + j, 1);
+                                uint4& x = cur[ci][sl];
+                                x = make_uint4(xam(x.x, m, sv.x), xam(x.y, m, sv.y), xam(x.z, m, sv.z), xam(x.w, m, sv.w));
+                            }
+                    }
+                }
+            }
+#pragma unroll
+            for (int ci = 0; ci < CG; ++ci)
+                if (c0 + ci < ncols) {
+                    tile(S, ci)[0] = cur[ci][0];
+                    tile(S, ci)[256] = cur[ci][1];
+                }
+#pragma unroll
+            for (int ci = 0; ci < CG; ++ci) {
+                cur[ci][0] = nxt[ci][0];
+                cur[ci][1] = nxt[ci][1];
+            }
+        }
+    }
+}
+
+// The same on a row-major DB [nrec][16 q16 bytes]: a thread per 16 bytes of a
+// record.  Workgroup (x, y) takes pieces [16 y, 16 y + P) of rpb consecutive
+// records (P = min(q16, 16) pieces per row of the workgroup, rpb = 256 / P),
+// stages those pieces of the kt <= 64 messages in LDS and walks the keys,
+// testing the record's bit.  Row-major handles and the plain device entry
+// point; untuned.
+__global__ __launch_bounds__(256) void k_xor_scatter_rows(const uint32_t* __restrict__ bits, uint64_t wpk,
+                                                           uint4* __restrict__ db, uint64_t nrec, uint32_t q16,
+                                                           const uint4* __restrict__ msgs, uint32_t kt, uint32_t P,
+                                                           uint32_t rpb) {
+    __shared__ uint4 m[kScatterKT][16];
+    const uint32_t t = threadIdx.x, p0 = 16 * blockIdx.y;
+    for (uint32_t i = t; i < kt * P; i += 256) {
+        const uint32_t k = i / P, p = i % P;
+        m[k][p] = p0 + p < q16 ? msgs[(uint64_t)k * q16 + p0 + p] : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    const uint32_t pc = t % P, rl = t / P;
+    const uint64_t rec = (uint64_t)blockIdx.x * rpb + rl;
+    if (rl >= rpb || rec >= nrec || p0 + pc >= q16) return;
+    uint4 acc = db[rec * q16 + p0 + pc];
+    for (uint32_t k = 0; k < kt; ++k) {
+        const uint32_t bit = (bits[(uint64_t)k * wpk + (rec >> 5)] >> (rec & 31)) & 1u;
+        acc = x4am(acc, m[k][pc], 0u - bit);
+    }
+    db[rec * q16 + p0 + pc] = acc;
+}
+
+template <int CG>
+static hipError_t scatter_sliced_cg(const dpfh::ScatterPlan& p, const uint32_t* bits, uint64_t wpk, uint8_t* dbs,
+                                    uint64_t nrec, uint64_t rec_bytes, const uint8_t* msgs, hipStream_t st) {
+    for (uint64_t tile = 0; tile < p.key_tiles(); ++tile) {
+        const dpfh::ScatterUnit k = p.unit(tile, 0);
+        for (uint64_t l = 0; l < p.launches(); ++l) {
+            hipLaunchKernelGGL(k_scatter_sliced<CG>, dim3((uint32_t)p.blocks(l)), dim3(256), 0, st, bits + k.k0 * wpk,
+                               wpk, reinterpret_cast<uint4*>(dbs), nrec, p.nsg, p.C,
+                               reinterpret_cast<const uint4*>(msgs + k.k0 * rec_bytes), (uint32_t)(rec_bytes / 16),
+                               (uint32_t)(k.k1 - k.k0), p.run, p.ncg, p.first(l));
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_scatter_sliced(const uint32_t* bits, uint64_t words_per_key, uint8_t* dbs, uint64_t nrec,
+                                 uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes) || words_per_key % 4 != 0 || nrec > words_per_key * 32) return hipErrorInvalidValue;
+    if (nkeys == 0 || nrec == 0) return hipSuccess;
+    const dpfh::ScatterPlan p =
+        dpfh::plan_scatter(nrec, (uint32_t)(rec_bytes / 32), nkeys, (uint32_t)cu_count_fold(),
+                           g_fold_blocks.load(std::memory_order_relaxed), fold_max_sg());
+    switch (p.cols) {
+        case 1: return scatter_sliced_cg<1>(p, bits, words_per_key, dbs, nrec, rec_bytes, msgs, st);
+        case 2: return scatter_sliced_cg<2>(p, bits, words_per_key, dbs, nrec, rec_bytes, msgs, st);
+        case 3: return scatter_sliced_cg<3>(p, bits, words_per_key, dbs, nrec, rec_bytes, msgs, st);
+        default: return scatter_sliced_cg<4>(p, bits, words_per_key, dbs, nrec, rec_bytes, msgs, st);
+    }
+}
+
+hipError_t launch_scatter_rows(const uint32_t* bits, uint64_t words_per_key, uint8_t* db, uint64_t nrec,
+                               uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st) {
+    if (!rec_bytes_ok(rec_bytes) || words_per_key % 4 != 0 || nrec > words_per_key * 32) return hipErrorInvalidValue;
+    if (nkeys == 0 || nrec == 0) return hipSuccess;
+    const uint32_t q16 = (uint32_t)(rec_bytes / 16), P = q16 < 16 ? q16 : 16, rpb = 256 / P;
+    const uint64_t per = (uint64_t)rpb << 30;                  // records per launch: <= 2^30 workgroups in x
+    for (uint64_t k0 = 0; k0 < nkeys; k0 += dpfh::kScatterKeyTile) {
+        const uint32_t kt = (uint32_t)std::min<uint64_t>(dpfh::kScatterKeyTile, nkeys - k0);
+        for (uint64_t r0 = 0; r0 < nrec; r0 += per) {
+            // (r0 is a multiple of 32: the launch's selection words start at word r0 / 32 of each row.)
+            const uint64_t n = std::min(per, nrec - r0);
+            hipLaunchKernelGGL(k_xor_scatter_rows, dim3((uint32_t)((n + rpb - 1) / rpb), (q16 + 15) / 16), dim3(256), 0,
+                               st, bits + k0 * words_per_key + r0 / 32, words_per_key,
+                               reinterpret_cast<uint4*>(db + r0 * rec_bytes), n, q16,
+                               reinterpret_cast<const uint4*>(msgs + k0 * rec_bytes), kt, P, rpb);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
 }
 
 namespace {

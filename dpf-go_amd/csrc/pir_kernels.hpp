@@ -1,5 +1,7 @@
-// pir_kernels.hpp — launcher for the XOR fold (pir_kernels.hip): the PIR
-// answer and the general-payload streaming consumer of EvalFull output.
+// pir_kernels.hpp — launchers for the XOR fold (pir_kernels.hip): the PIR
+// answer and the general-payload streaming consumer of EvalFull output; for
+// the resident DB's in-place updates; and for the fold's dual, the private
+// write (messages XORed into the selected records).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +64,20 @@ hipError_t launch_update_rows(uint8_t* db, uint64_t nrec, uint64_t rec_bytes, co
                               uint64_t n, hipStream_t st);
 hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
                               uint8_t* out, hipStream_t st);
+
+// Private writes, the dual of the fold (k_scatter_sliced; k_xor_scatter_rows
+// on a row-major DB): record i ^= XOR over keys k < nkeys with bit i of
+// bits[k * words_per_key ...] set of msgs[k * rec_bytes ..), for i < nrec.
+// Selection bits at positions >= nrec are ignored, so the sliced layout's
+// padding stays zero.  Keys go in tiles of dpfh::kScatterKeyTile, one pass
+// over the DB each, planned by pir_scatter_plan.hpp under set_fold_limits'
+// max_blocks (workgroups per launch) and max_sg (super-groups per workgroup).
+// No workspace, no atomics, asynchronous on st.  bits, dbs / db and msgs
+// 16-byte aligned; words_per_key a multiple of 4 covering nrec bits.
+hipError_t launch_scatter_sliced(const uint32_t* bits, uint64_t words_per_key, uint8_t* dbs, uint64_t nrec,
+                                 uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st);
+hipError_t launch_scatter_rows(const uint32_t* bits, uint64_t words_per_key, uint8_t* db, uint64_t nrec,
+                               uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st);
 
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per

@@ -107,6 +107,11 @@ SIGNATURES = {
     "dpf_pir_answer_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_db_update_sliced_wide_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
     "dpf_pir_db_gather_sliced_wide_dev": (_int, [_int, _vp, _u64, _sz, _vp, _sz, _vp, _vp]),
+    "dpf_xor_scatter_dev": (_int, [_int, _vp, _sz, _sz, _vp, _vp, _u64, _sz, _vp]),
+    "dpf_xor_scatter_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _vp, _vp, _u64, _sz, _vp]),
+    "dpf_pir_write_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_write_sliced_wide_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_write": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_pir_db_create_wide": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_rec_bytes": (_sz, [_vp]),
     "dpf_pir_db_nrec": (_u64, [_vp]),
@@ -590,6 +595,38 @@ def pir_db_gather_sliced_wide_dev(d_dbs, nrec: int, rec_bytes: int, d_idx, n: in
                                                    _stream_handle(stream)))
 
 
+def xor_scatter_dev(d_bits, bits_stride: int, nkeys: int, d_msgs, d_db, nrec: int, rec_bytes: int, device: int = 0,
+                    stream=None) -> None:
+    """Row-major DB record i ^= XOR of the messages d_msgs[k] (rec_bytes each)
+    whose EvalFull output k has bit i set, i < nrec, in place (dpf_xor_scatter_dev)."""
+    _check(lib().dpf_xor_scatter_dev(device, _ptr(d_bits), bits_stride, nkeys, _ptr(d_msgs), _ptr(d_db), nrec,
+                                     rec_bytes, _stream_handle(stream)))
+
+
+def xor_scatter_sliced_wide_dev(d_bits, bits_stride: int, nkeys: int, d_msgs, d_dbs, nrec: int, rec_bytes: int,
+                                device: int = 0, stream=None) -> None:
+    """xor_scatter_dev over the wide bit-sliced DB (bits past nrec ignored: the padding stays zero)."""
+    _check(lib().dpf_xor_scatter_sliced_wide_dev(device, _ptr(d_bits), bits_stride, nkeys, _ptr(d_msgs), _ptr(d_dbs),
+                                                 nrec, rec_bytes, _stream_handle(stream)))
+
+
+def pir_write_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_msgs, d_db, nrec: int, rec_bytes: int, d_work,
+                       prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """Private write into the row-major DB slice of subtree (prefix_bits,
+    prefix): the subtree EvalFull of the keys, then xor_scatter_dev of their
+    messages (d_work: pir_workspace_size bytes)."""
+    _check(lib().dpf_pir_write_wide_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix, _ptr(d_msgs),
+                                        _ptr(d_db), nrec, rec_bytes, _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_write_sliced_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_msgs, d_dbs, nrec: int, rec_bytes: int,
+                              d_work, prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """pir_write_wide_dev over the wide bit-sliced DB slice."""
+    _check(lib().dpf_pir_write_sliced_wide_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix,
+                                               _ptr(d_msgs), _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work),
+                                               _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -641,6 +678,20 @@ class PirDB:
         if r.size != ix.size * self.rec_bytes:
             raise ValueError("recs must hold len(idx) records of %d bytes" % self.rec_bytes)
         _check(lib().dpf_pir_db_update(self._h, ix.ctypes.data_as(_u64p), _buf(r), ix.size))
+
+    def write(self, keys, msgs) -> None:
+        """Private write: record i ^= XOR of the messages msgs[k] (rec_bytes
+        each) whose key has bit i of its EvalFull set.  Two servers applying
+        the same messages under their key shares change the XOR of their DBs
+        by msgs[k] at alpha_k only.  A short key raises DPFPanic and changes
+        nothing."""
+        kk = np.ascontiguousarray(keys, dtype=np.uint8)
+        if kk.ndim != 2:
+            raise ValueError("keys must be a (nkeys, key_len) array")
+        m = np.ascontiguousarray(msgs, dtype=np.uint8).reshape(-1)
+        if m.size != kk.shape[0] * self.rec_bytes:
+            raise ValueError("msgs must hold len(keys) messages of %d bytes" % self.rec_bytes)
+        _check(lib().dpf_pir_db_write(self._h, _buf(kk), kk.shape[1], kk.shape[0], _buf(m)))
 
     def read(self, idx) -> np.ndarray:
         """The records idx[i] as the DB now holds them, (len(idx), rec_bytes), in the caller's order."""

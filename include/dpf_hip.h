@@ -331,6 +331,47 @@ int dpf_pir_db_update_sliced_wide_dev(int device, uint8_t* d_dbs, uint64_t nrec,
                                       const uint64_t* d_idx, const uint8_t* d_recs, size_t n, void* stream);
 int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
                                       const uint64_t* d_idx, size_t n, uint8_t* d_out, void* stream);
+/* Private writes, the dual of the fold and the server step of a two-server
+ * private write: for every key k with a message m_k,
+ *   d_db / d_dbs record i ^= XOR over k < nkeys with bit i of d_bits[k] set
+ *                            of d_msgs[k],   for i < nrec
+ * (bit i = bit i%8 of byte i/8, EvalFull's layout).  Two servers that apply
+ * the same messages under their shares of the keys change the XOR of their
+ * DBs by m_k at alpha_k only.  The messages themselves are not hidden.
+ * d_bits [nkeys][bits_stride] (bits_stride a multiple of 16, nrec <=
+ * 8*bits_stride), d_msgs [nkeys][rec_bytes], rec_bytes a positive multiple of
+ * 32 up to DPF_PIR_MAX_REC_BYTES; d_bits, d_msgs and the DB 16-byte aligned
+ * and not null (else DPF_ERR_PARAM, checked before any device call);
+ * nkeys == 0 or nrec == 0 returns DPF_OK without a launch.  Asynchronous on
+ * `stream`, no workspace, no atomics.  dpf_xor_scatter_dev takes the
+ * row-major DB [nrec][rec_bytes], dpf_xor_scatter_sliced_wide_dev the wide
+ * sliced layout (32 is its C = 1 case).  Selection bits at positions >= nrec
+ * are ignored whatever the caller left there, so the padding of the last
+ * super-group stays zero ("records past nrec read as 0").  In the sliced
+ * layout the 32 records of a word are the 32 selection bits of one u32 of a
+ * key's row, so the kernel transposes nothing: each 8-KiB tile (super-group,
+ * column) is read once and written once per tile of 64 keys, and more keys
+ * are further passes over the DB.  dpf_set_fold_limits bounds its launches
+ * too (workgroups per launch; super-groups per workgroup). */
+int dpf_xor_scatter_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys, const uint8_t* d_msgs,
+                        uint8_t* d_db, uint64_t nrec, size_t rec_bytes, void* stream);
+int dpf_xor_scatter_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                    const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                    void* stream);
+/* The subtree EvalFull of the keys into d_work, then the scatter: the dual
+ * of dpf_pir_answer_wide_dev / dpf_pir_answer_sliced_wide_dev, with their
+ * slice contract (d_db holds nrec <= 2^(logN-prefix_bits) records of subtree
+ * (prefix_bits, prefix), more is DPF_ERR_PARAM) and workspace
+ * (dpf_pir_workspace_size(nkeys, logN, prefix_bits) bytes, 16-byte aligned).
+ * Always a tree launch followed by the scatter; DPF_PIR_FUSED has no part in
+ * it.  d_keys, d_msgs, the DB and d_work not null, the last three 16-byte
+ * aligned (else DPF_ERR_PARAM before any device call). */
+int dpf_pir_write_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                           uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec,
+                           size_t rec_bytes, void* d_work, void* stream);
+int dpf_pir_write_sliced_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                                  uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_dbs,
+                                  uint64_t nrec, size_t rec_bytes, void* d_work, void* stream);
 /* Tuning / test limits of the XOR fold launches (process-wide; 0 = default):
  * at most max_blocks workgroups per fold launch (default and maximum 1024),
  * and at most max_sg_per_block super-groups of 256 records per matrix-core
@@ -394,6 +435,15 @@ uint64_t dpf_pir_db_nrec(void* handle);
  * (DPF_PIR_FOLD=lds) a plain scatter.  Synchronous. */
 int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, size_t n);
 int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out);
+/* Private write to a resident DB: every shard applies the batch to its slice
+ * (dpf_pir_write_sliced_wide_dev; row-major shards dpf_pir_write_wide_dev).
+ * keys [nkeys][key_len], msgs [nkeys][dpf_pir_db_rec_bytes(handle)].  A short
+ * key is DPF_ERR_KEYLEN and nothing is changed.  Per shard the batch runs on
+ * the device's stream under that device's mutex, so a concurrent
+ * dpf_pir_answer sees a shard wholly before or wholly after the batch; writes
+ * to different shards are not atomic with respect to each other, as for
+ * dpf_pir_db_update.  Synchronous. */
+int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t key_len, size_t nkeys, const uint8_t* msgs);
 void dpf_pir_db_free(void* handle);
 
 #ifdef __cplusplus
