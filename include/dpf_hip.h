@@ -123,7 +123,11 @@ int dpf_evalfull_split(const uint8_t* key, size_t key_len, uint32_t logN, uint8_
 int dpf_evalfull_batch_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
                            uint8_t* d_out, void* d_work, void* stream);
 /* The subtree at depth prefix_bits, index prefix of every key: 2^(logN-3-
- * prefix_bits) bytes per key at d_out + k*that (logN-7 >= prefix_bits). */
+ * prefix_bits) bytes per key at d_out + k*that (logN-7 >= prefix_bits).
+ * dpf_workspace_size counts scratch for the whole tree and outgrows any
+ * device at deep logN; a subtree call (this one, dpf_expand_keys_dev and
+ * dpf_evalfull_expanded_dev) uses at most dpf_pir_workspace_size(nkeys,
+ * logN, prefix_bits) bytes of d_work. */
 int dpf_evalfull_subtree_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
                              uint32_t prefix_bits, uint64_t prefix, uint8_t* d_out, void* d_work, void* stream);
 /* Batched Eval on HBM buffers.  d_work holds work_bytes; with

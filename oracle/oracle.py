@@ -143,6 +143,57 @@ def eval_batch(keys: np.ndarray, xs: np.ndarray, logN: int, nthreads: int = 1, a
     return out
 
 
+def reroot_key(key, logN: int, prefix_bits: int, prefix: int) -> bytes:
+    """The key of the subtree (prefix_bits, prefix) of `key`: its root (s, t)
+    walked down prefix_bits levels along prefix (evalFullRecursive's own
+    steps, dpf.go:213-241: t is a byte tested != 0, the t correction words
+    are XORed in as bytes), followed by the remaining levels' records, the
+    final CW and whatever trails it.  The result is a key for logN -
+    prefix_bits whose EvalFull is the subtree's slice of the deep key's,
+    byte for byte, for malformed keys too; evalfull_batch and
+    pir_answer_batch then serve deep subtrees unchanged."""
+    k = bytes(key)
+    stop = max(logN - 7, 0)
+    assert 0 <= prefix_bits <= stop and 0 <= prefix < (1 << prefix_bits)
+    assert len(k) >= 17 + 18 * prefix_bits + 16
+    s, t = k[:16], k[16]
+    for i in range(prefix_bits):
+        right = (prefix >> (prefix_bits - 1 - i)) & 1
+        c = int.from_bytes(mmo(bool(right), s), "little")
+        ct = c & 1                                   # bit 0 of byte 0 (dpf.go:46-52)
+        c &= ~1
+        if t != 0:
+            rec = k[17 + 18 * i: 17 + 18 * i + 18]
+            c ^= int.from_bytes(rec[:16], "little")
+            ct ^= rec[17] if right else rec[16]
+        s, t = c.to_bytes(16, "little"), ct
+    return s + bytes([t]) + k[17 + 18 * prefix_bits:]
+
+
+def evalfull_subtree_by_points(key, logN: int, prefix_bits: int, prefix: int, nthreads: int = 8) -> np.ndarray:
+    """The same slice by another road: Eval (dpf.go:171-211) of every point
+    (prefix << span) + j of the subtree, packed LSB-first -> uint8 array of
+    2^span / 8 bytes (span = logN - prefix_bits >= 7)."""
+    span = logN - prefix_bits
+    assert span >= 7 and 0 <= prefix < (1 << prefix_bits)
+    xs = ((prefix << span) + np.arange(1 << span, dtype=np.uint64)).reshape(1, -1)
+    bits = eval_batch_split(_u8(key).reshape(1, -1), xs, logN, nthreads)
+    return np.packbits(bits.reshape(-1), bitorder="little")
+
+
+def eval_batch_split(keys: np.ndarray, xs: np.ndarray, logN: int, nthreads: int = 8) -> np.ndarray:
+    """eval_batch of few keys with many points each: oracle_eval_batch gives a
+    key to one thread, so each key's points go out as nthreads rows."""
+    kk = np.ascontiguousarray(keys, dtype=np.uint8)
+    x = np.ascontiguousarray(xs, dtype=np.uint64)
+    n, p = x.shape
+    parts = max(1, min(nthreads, p))
+    while p % parts:
+        parts -= 1
+    out = eval_batch(np.repeat(kk, parts, axis=0), x.reshape(n * parts, p // parts), logN, nthreads)
+    return out.reshape(n, p)
+
+
 def pir_answer(key: bytes, logN: int, db: np.ndarray, rec_lo: int, nrec: int) -> bytes:
     k = _u8(key)
     d = np.ascontiguousarray(db, dtype=np.uint8)

@@ -343,6 +343,46 @@ def test_host_path_matches_oracle(host_shim, logN, isa, monkeypatch):
     assert np.array_equal(_host_eval(host_shim, keys, xs, logN), oracle.eval_batch(keys, xs, logN, nthreads=4))
 
 
+@pytest.mark.parametrize("isa", ["auto", "aesni"])
+@pytest.mark.parametrize("logN", [21, 31, 32, 33, 40, 48, 62, 63, 64, 70])
+def test_host_eval_deep_domains(host_shim, logN, isa, monkeypatch):
+    """Host Eval (where every single dpf_eval goes by default) at and past the
+    32-bit boundary of the domain: 8 keys (4 alphas, both shares; arbitrary key
+    bytes above logN 63, where Gen makes none, dpf.go:72-74) x 300 points
+    against the oracle.  Each key's alpha, alpha^1 and alpha^128, points with
+    bits above logN set (ignored, dpf.go:194), whole 64-bit words, and points
+    uniform over the domain."""
+    import oracle
+    monkeypatch.setenv("DPF_HOST_ISA", isa)
+    rng = np.random.default_rng(1000 + logN)
+    nk, ppk = 8, 300
+    if logN <= 63:
+        al, s0, s1 = synth.key_seeds(4, logN, first=2100 + logN)
+        ka, kb = dpf.gen_batch_seeded(al, logN, s0, s1)
+        keys, alphas = np.concatenate([ka, kb]), np.concatenate([al, al])
+    else:
+        keys = rng.integers(0, 256, (nk, dpf.key_len(logN)), dtype=np.uint8)
+        alphas = rng.integers(0, 1 << 64, nk, dtype=np.uint64)
+    mask = np.uint64((1 << min(logN, 64)) - 1)
+    xs = rng.integers(0, 1 << 64, (nk, ppk), dtype=np.uint64)
+    xs[:, 150:] &= mask                                   # uniform over the domain
+    xs[:, 0] = alphas
+    xs[:, 1] = alphas ^ np.uint64(1)
+    xs[:, 2] = alphas ^ np.uint64(128)
+    if logN < 64:
+        xs[:, 3] = alphas | np.uint64(1 << logN)          # alpha with the first ignored bit set
+        xs[:, 4] = alphas | ~mask
+        xs[:, 5:10] |= ~mask
+    if logN <= 63:
+        xs[4:] = xs[:4]                                   # both shares answer the same points
+    if logN > 32:
+        assert (((xs >> np.uint64(32)) != 0).mean(axis=1) > 0.5).all()   # real 64-bit points
+    want = oracle.eval_batch(keys, xs, logN, nthreads=4)
+    assert np.array_equal(_host_eval(host_shim, keys, xs, logN), want)
+    if logN <= 63:
+        assert np.array_equal(want[:4] ^ want[4:], ((xs[:4] & mask) == alphas[:4, None]).astype(np.uint8))
+
+
 @pytest.mark.parametrize("logN", [5, 9, 13])
 def test_host_path_exactness_rules(host_shim, logN):
     """SURVEY §8c's rules on malformed keys: byte-valued t (not bit 0), an
