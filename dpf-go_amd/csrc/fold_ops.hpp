@@ -1,11 +1,14 @@
-// fold_ops.hpp — pieces of the XOR fold shared by the fold kernels
-// (pir_kernels.hip) and the fused PIR kernel (pir_fused.hip): the answers'
-// clearing, the FP4 operands of the matrix-core fold (layout and exactness:
-// pir_kernels.hip, "The fold as a GF(2) matrix product") and the partials'
-// reduction launch.
+// fold_ops.hpp — pieces of the XOR fold shared by its translation units
+// (pir_fold_rows.hip, pir_fold_sliced.hip, pir_db_ops.hip, pir_kernels.hip)
+// and the fused PIR kernel (pir_fused.hip): the answers' clearing, the bitwise
+// and load helpers, the FP4 operands of the matrix-core fold (layout and
+// exactness: pir_fold_sliced.hip, "The fold as a GF(2) matrix product"), the
+// partials' reduction launch and the launchers' shared host state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "pir_fold_plan.hpp"
 
 namespace dpfk {
 
@@ -15,6 +18,48 @@ __device__ __forceinline__ void zero_answers(uint32_t* zero, uint64_t words) {
     if (zero == nullptr) return;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (uint64_t)gridDim.x * blockDim.x)
         zero[t] = 0;
+}
+
+// v_bitop3_b32 truth tables: src0 = 0xF0, src1 = 0xCC, src2 = 0xAA.
+constexpr uint8_t kTT0 = 0xF0, kTT1 = 0xCC, kTT2 = 0xAA;
+__device__ __forceinline__ uint32_t x3(uint32_t a, uint32_t b, uint32_t c) {
+    return __builtin_amdgcn_bitop3_b32(a, b, c, kTT0 ^ kTT1 ^ kTT2);
+}
+// a ^ (b & m)
+__device__ __forceinline__ uint32_t xam(uint32_t a, uint32_t b, uint32_t m) {
+    return __builtin_amdgcn_bitop3_b32(a, b, m, kTT0 ^ (kTT1 & kTT2));
+}
+__device__ __forceinline__ uint4 x4(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
+__device__ __forceinline__ uint4 x4am(uint4 a, uint4 b, uint32_t m) {
+    return make_uint4(xam(a.x, b.x, m), xam(a.y, b.y, m), xam(a.z, b.z, m), xam(a.w, b.w, m));
+}
+// Workgroup barrier of the folds' LDS staging: the plain barrier.  The
+// compiler keeps a global prefetch in flight across it; fencing the local
+// address space only measured identical (r05, profiles/r05/fold_barrier).
+__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
+
+// Bits of chunk cc's records below nrec, for word 0 (records 0..31) and 1;
+// none when the chunk is not the caller's (live = false).  Arithmetic, not
+// branches: a branch here splits the lookup block and the register
+// allocator then spills the table reads around it.
+__device__ __forceinline__ uint2 valid_mask(uint64_t cc, uint64_t nrec, bool live = true) {
+    uint64_t v = nrec > cc * 64 ? nrec - cc * 64 : 0;
+    v = live ? (v < 64 ? v : 64) : 0;
+    const uint32_t lo = v < 32 ? (uint32_t)v : 32u, hi = v > 32 ? (uint32_t)v - 32u : 0u;
+    return make_uint2((uint32_t)((1ull << lo) - 1), (uint32_t)((1ull << hi) - 1));
+}
+
+// A streamed 16-byte operand; NT: a nontemporal load (the `nt` cache policy),
+// for DB slices too large to stay in the caches between batches (fold_ntdb).
+typedef uint32_t fold_nt4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 fold_ld(const uint4* p) {
+    if constexpr (NT) {
+        const fold_nt4 v = __builtin_nontemporal_load(reinterpret_cast<const fold_nt4*>(p));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    } else {
+        return *p;
+    }
 }
 
 typedef int fold_v8i __attribute__((ext_vector_type(8)));
@@ -53,7 +98,14 @@ __device__ __forceinline__ uint32_t u4w(const uint4& v, int t) { return t == 0 ?
 constexpr int kFoldFp4 = 4;         // cbsz / blgp format code of e2m1
 constexpr int kE8M0One = 127;       // block scale 2^0
 
-constexpr uint64_t kFoldMaxBlocks = 1024;          // workgroups per launch (partials area)
+using dpfh::kFoldMaxBlocks;
+
+// What every fold launcher plans from (pir_kernels.hip): one snapshot of
+// set_fold_limits' values, taken once per public call, and the environment
+// knobs, read once per process.  (The third input, the calling thread's CU
+// budget, is cu_count() of dpf_kernels.hpp.)
+dpfh::FoldLimits fold_limits();
+const dpfh::FoldKnobs& fold_knobs();
 
 // XOR nparts workgroup partials into the answers (stream-ordered after the fold).
 hipError_t launch_xor_parts(const uint32_t* parts, uint64_t nparts, uint32_t nkeys, uint32_t pkeys,

@@ -1,24 +1,20 @@
-// pir_kernels.hpp — launchers for the XOR fold (pir_kernels.hip): the PIR
-// answer and the general-payload streaming consumer of EvalFull output; for
-// the resident DB's in-place updates; and for the fold's dual, the private
-// write (messages XORed into the selected records).
+// pir_kernels.hpp — launchers for the XOR fold (pir_fold_rows.hip,
+// pir_fold_sliced.hip; shared parts in pir_kernels.hip): the PIR answer and
+// the general-payload streaming consumer of EvalFull output; for the resident
+// DB's in-place updates; and for the fold's dual, the private write (messages
+// XORed into the selected records), both in pir_db_ops.hip.  How each launcher
+// sizes its launches: pir_fold_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define DPF_FOLD_PLAN 1   // plan_fold() below (tools/fold_bench.hip)
+#include "pir_fold_plan.hpp"
 
 namespace dpfk {
 
-// How launch_pir_fold covers (rec_bytes, nkeys): `cols` 32-byte columns per
-// pass (1, 2, 4 or 8 = the whole record; 1 with `col_passes` = rec_bytes/32
-// for other widths), `keys_per_pass` keys per DB read, the direct kernel or
-// Four-Russians with `kw` 64-key lane groups sharing each table.
-struct FoldPlan {
-    uint32_t cols, col_passes, keys_per_pass, kw;
-    bool direct;
-};
-FoldPlan plan_fold(uint64_t rec_bytes, uint32_t nkeys);
+// How launch_pir_fold covers (rec_bytes, nkeys).
+using dpfh::FoldPlan;
+using dpfh::plan_fold;
 
 // ans[k][0 .. rec_bytes) = XOR of the records db[i] (rec_bytes each, a
 // multiple of 32; i < nrec) whose bit i is set in bits[k * words_per_key
@@ -41,7 +37,7 @@ hipError_t launch_pir_fold(const uint32_t* bits, uint64_t words_per_key, const u
 // records [256 S0, ...) into dbs + S0 * 256 * rec_bytes writes what slicing
 // the whole DB writes there.  Same bits / parts / ans contract as
 // launch_pir_fold; ans is [nkeys][rec_bytes].
-constexpr uint64_t kFoldMaxRecBytes = 32768;
+using dpfh::kFoldMaxRecBytes;   // 32768
 uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes);
 hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st);
 hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,

@@ -1,4 +1,4 @@
-// pir_scatter_plan.hpp — how launch_scatter_sliced (pir_kernels.hip) covers a
+// pir_scatter_plan.hpp — how launch_scatter_sliced (pir_db_ops.hip) covers a
 // private write: which super-groups, columns and keys each k_scatter_sliced
 // workgroup takes, and how the workgroups fall into launches.  Pure functions
 // of (nrec, C, nkeys, CU count, limits); host-only and header-only (no HIP), so
@@ -9,13 +9,13 @@
 
 #include <algorithm>
 
+#include "pir_fold_plan.hpp"
+
 namespace dpfh {
 
 constexpr uint32_t kScatterKeyTile = 64;          // KT: keys per pass over the DB (a thread's message bits: 2 words)
 constexpr uint32_t kScatterMaxCols = 4;           // 32-byte columns per workgroup (they share the staged selection words)
 constexpr uint32_t kScatterPerCu = 4;             // workgroups per CU the run length aims at
-constexpr uint32_t kScatterMaxBlocks = 1024;      // dpf_set_fold_limits' defaults
-constexpr uint32_t kScatterMaxSg = 1u << 15;
 
 // One workgroup's work: super-groups [s0, s1) of columns [c0, c1), keys [k0, k1).
 struct ScatterUnit {
@@ -51,9 +51,9 @@ struct ScatterPlan {
     }
 };
 
-// max_blocks / max_sg: dpf_set_fold_limits' values (0 = the defaults above;
-// larger ones are cut to them).  C >= 1.  Nothing to do (units == 0) when
-// nrec == 0 or nkeys == 0.
+// max_blocks / max_sg: dpf_set_fold_limits' values (0 = the defaults of
+// pir_fold_plan.hpp; larger ones are cut to them).  C >= 1.  Nothing to do
+// (units == 0) when nrec == 0 or nkeys == 0.
 inline ScatterPlan plan_scatter(uint64_t nrec, uint32_t C, uint64_t nkeys, uint32_t cus, uint32_t max_blocks,
                                 uint32_t max_sg) {
     ScatterPlan p;
@@ -61,8 +61,8 @@ inline ScatterPlan plan_scatter(uint64_t nrec, uint32_t C, uint64_t nkeys, uint3
     p.nkeys = nkeys;
     p.C = C;
     if (p.nsg == 0 || nkeys == 0 || C == 0) return p;
-    const uint64_t cap = max_blocks == 0 || max_blocks > kScatterMaxBlocks ? kScatterMaxBlocks : max_blocks;
-    const uint64_t msg = max_sg == 0 || max_sg > kScatterMaxSg ? kScatterMaxSg : max_sg;
+    const FoldLimits lim = clamp_fold_limits(max_blocks, max_sg);
+    const uint64_t cap = lim.max_blocks, msg = lim.max_sg;
     // Column groups of equal size (5 columns: 3 + 2, not 4 + 1).
     p.ncg = (C + kScatterMaxCols - 1) / kScatterMaxCols;
     p.cols = (C + p.ncg - 1) / p.ncg;

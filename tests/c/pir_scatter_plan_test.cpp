@@ -29,8 +29,8 @@ static int g_fail = 0;
 static void check(uint64_t nrec, uint32_t C, uint64_t nkeys, uint32_t cus, uint32_t max_blocks, uint32_t max_sg) {
     const ScatterPlan p = plan_scatter(nrec, C, nkeys, cus, max_blocks, max_sg);
     const uint64_t nsg = (nrec + 255) / 256;
-    const uint64_t cap = max_blocks ? max_blocks : kScatterMaxBlocks;
-    const uint64_t msg = max_sg ? max_sg : kScatterMaxSg;
+    const uint64_t cap = max_blocks ? max_blocks : kFoldMaxBlocks;
+    const uint64_t msg = max_sg ? max_sg : kFoldMaxSg;
     const uint64_t tiles = p.key_tiles();
 #define AT "nrec=%llu C=%u nkeys=%llu blocks=%u sg=%u", (unsigned long long)nrec, C, (unsigned long long)nkeys, max_blocks, max_sg
     if (nsg == 0 || nkeys == 0) {

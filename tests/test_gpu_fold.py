@@ -46,7 +46,7 @@ def _fold(full_dev, stride, nk, payload, nrec, rec_bytes):
     return d_ans.cpu().numpy().reshape(nk, rec_bytes)
 
 
-# Every branch of the fold plan (pir_kernels.hip plan_fold): the direct kernel
+# Every branch of the fold plan (pir_fold_plan.hpp plan_fold): the direct kernel
 # (<= 16 keys) at 1/2/4/8 columns, Four-Russians with 1/2/4 lane groups per
 # table, several DB passes (> 256 keys, or C = 8 beyond 64 keys), widths that
 # run column by column (96, 160 B), ragged record counts, nrec = 1 and nrec = 0

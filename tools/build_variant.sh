@@ -12,13 +12,14 @@ mkdir -p "$O"
 make -s -C "$REPO/dpf-go_amd" > /dev/null
 HIPCC=/opt/rocm/bin/hipcc
 CXX=(-O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=gfx950)
-for f in dpf_kernels bs_kernels pir_kernels dpf_capi; do
+HIP=(dpf_kernels bs_kernels pir_kernels pir_fold_rows pir_fold_sliced pir_db_ops dpf_capi)
+for f in "${HIP[@]}"; do
   X=""; [ "$f" = dpf_kernels ] && X="$KFLAGS"
   # shellcheck disable=SC2086
   $HIPCC "${CXX[@]}" $FLAGS $X -c "$REPO/dpf-go_amd/csrc/$f.hip" -o "$O/$f.o" &
 done
 wait
+OBJ=("${HIP[@]/#/$O/}")
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$L/variants/libdpf_hip_$NAME.so" \
-    "$O/dpf_kernels.o" "$O/bs_kernels.o" "$O/pir_kernels.o" "$O/dpf_capi.o" "$L/host_gen.o" "$L/host_eval.o" \
-    "$L/experimental_none.o" -lpthread
+    "${OBJ[@]/%/.o}" "$L/host_gen.o" "$L/host_eval.o" "$L/experimental_none.o" -lpthread
 echo "$L/variants/libdpf_hip_$NAME.so"

@@ -1,9 +1,9 @@
-// fold_bench.hip — isolates the XOR fold (pir_kernels.hip) at configs[4]
+// fold_bench.hip — isolates the XOR fold (pir_fold_rows.hip, pir_fold_sliced.hip) at configs[4]
 // shape by default (2^24 records x 32 B, 64 keys, random selection bits laid
 // out as EvalFull writes them), times it with HIP events and checks 2 keys'
 // answers against a plain host fold.  Args: [nkeys] [rec_bytes] [log2 nrec].
-// Build with -DFOLD_SRC=<file> to A/B another revision (tools/ab/).  One
-// JSON line.
+// Build with -DFOLD_SRC=<file> to A/B a revision that had the fold in one
+// file (tools/ab/).  One JSON line.
 // Build (from tools/): hipcc --offload-arch=gfx950 -O3 -std=c++17 fold_bench.hip -o fold_bench
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -11,12 +11,16 @@
 #include <string.h>
 #include <vector>
 
-#ifndef FOLD_SRC
-#define FOLD_SRC "../dpf-go_amd/csrc/pir_kernels.hip"
-#endif
+#ifdef FOLD_SRC
 #include FOLD_SRC
+#else
+#define FOLD_SRC "../dpf-go_amd/csrc/pir_fold_{rows,sliced}.hip"
+#include "../dpf-go_amd/csrc/pir_kernels.hip"       // what the folds share: k_xor_parts, limits, knobs
+#include "../dpf-go_amd/csrc/pir_fold_rows.hip"
+#include "../dpf-go_amd/csrc/pir_fold_sliced.hip"
+#endif
 
-// pir_kernels.hip sizes its grids with dpfk::cu_count() (dpf_kernels.hip in
+// The fold sizes its grids with dpfk::cu_count() (dpf_kernels.hip in
 // the library): the whole device here.
 namespace dpfk {
 int cu_count() {
@@ -112,11 +116,7 @@ int main(int argc, char** argv) {
                 for (uint64_t b = 0; b < rec_bytes; ++b) want[b] ^= hdb[i * rec_bytes + b];
         bad += memcmp(want.data(), &a[(size_t)k * rec_bytes], rec_bytes) != 0;
     }
-#ifdef DPF_FOLD_PLAN
     const dpfk::FoldPlan p = dpfk::plan_fold(rec_bytes, nkeys);
-#else
-    struct { uint32_t cols, col_passes, keys_per_pass, kw; bool direct; } p{1, (uint32_t)(rec_bytes / 32), 64, 1, false};
-#endif
     const double bytes = (double)nrec * rec_bytes + (double)nkeys * nrec / 8;
     printf("{\"src\": \"%s\", \"nkeys\": %u, \"rec_bytes\": %llu, \"nrec\": %llu, \"kernel\": \"%s\", \"kw\": %u, "
            "\"col_passes\": %u, \"fold_us\": %.1f, \"GBs\": %.0f, \"db_reads\": %u, \"slice_db_us\": %.1f, \"ok\": %s}\n",
