@@ -872,7 +872,13 @@ int dpf_pir_db_slice_dev(int device, const uint8_t* d_db, uint64_t nrec, uint8_t
     return dpf_pir_db_slice_wide_dev(device, d_db, nrec, 32, d_dbs, stream);
 }
 
-static int check_rec_bytes(size_t rec_bytes) {
+// any: the _any entry points (a multiple of 4); else the _wide rule (of 32).
+static int check_rec_bytes(size_t rec_bytes, bool any = false) {
+    if (any) {
+        if (rec_bytes == 0 || rec_bytes % 4 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES)
+            return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 4, at most DPF_PIR_MAX_REC_BYTES");
+        return DPF_OK;
+    }
     if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES)
         return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be a positive multiple of 32, at most DPF_PIR_MAX_REC_BYTES");
     return DPF_OK;
@@ -885,8 +891,8 @@ static int check_rec_bytes(size_t rec_bytes) {
 // records take both in one launch (k_pir_fused) where g_pir_kernel selects it.
 static int pir_answer(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
                       uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes,
-                      uint8_t* d_ans, void* d_work, void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+                      uint8_t* d_ans, void* d_work, void* stream, bool any = false) {
+    if (int rc = check_rec_bytes(rec_bytes, any)) return rc;
     if (int rc = check_key(klen, logN)) return rc;
     const uint32_t stop = stop_of(logN);
     if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
@@ -950,6 +956,13 @@ int dpf_pir_answer_sliced_wide_dev(int device, const uint8_t* d_keys, size_t kle
                       stream);
 }
 
+int dpf_pir_answer_sliced_any_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                                  uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                                  size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream) {
+    return pir_answer(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_dbs, nrec, rec_bytes, d_ans, d_work,
+                      stream, true);
+}
+
 // The three fold entries behind their rec_bytes check: the shape and buffer
 // checks in the order they report (bits_stride, nrec, alignment, null), then
 // the fold on the caller's stream -- sliced: the matrix-core fold over the
@@ -993,15 +1006,29 @@ int dpf_xor_fold_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bits_
                     stream);
 }
 
+int dpf_xor_fold_sliced_any_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes, true)) return rc;
+    return xor_fold(true, rec_bytes > 32, device, d_bits, bits_stride, nkeys, d_dbs, nrec, rec_bytes, d_ans, d_work,
+                    stream);
+}
+
 // ---- records of rec_bytes = 32 C bytes over the sliced layout -------------
+// (and, by the _any entries, of any multiple of 4 bytes: the same launchers)
 size_t dpf_pir_db_sliced_size_wide(uint64_t nrec, size_t rec_bytes) {
     if (rec_bytes == 0 || rec_bytes % 32 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES) return 0;
     return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec, rec_bytes));
 }
 
-int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
-                              void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+size_t dpf_pir_db_sliced_size_any(uint64_t nrec, size_t rec_bytes) {
+    if (rec_bytes == 0 || rec_bytes % 4 != 0 || rec_bytes > DPF_PIR_MAX_REC_BYTES) return 0;
+    return std::max<size_t>(16, dpfk::pir_sliced_bytes(nrec, rec_bytes));
+}
+
+static int pir_db_slice(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs, void* stream,
+                        bool any) {
+    if (int rc = check_rec_bytes(rec_bytes, any)) return rc;
     if (nrec > 0 && (!d_db || !d_dbs)) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
     if (((uintptr_t)d_db | (uintptr_t)d_dbs) % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
     DeviceGuard g(device);
@@ -1009,10 +1036,21 @@ int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, si
     return DPF_OK;
 }
 
+int dpf_pir_db_slice_wide_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                              void* stream) {
+    return pir_db_slice(device, d_db, nrec, rec_bytes, d_dbs, stream, false);
+}
+
+int dpf_pir_db_slice_any_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                             void* stream) {
+    return pir_db_slice(device, d_db, nrec, rec_bytes, d_dbs, stream, true);
+}
+
 // Records of the sliced DB changed / read back in place: every argument is
 // checked before any device call.
-static int check_update_bufs(size_t rec_bytes, const void* d_dbs, const void* d_idx, const void* d_recs) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+static int check_update_bufs(size_t rec_bytes, const void* d_dbs, const void* d_idx, const void* d_recs,
+                             bool any = false) {
+    if (int rc = check_rec_bytes(rec_bytes, any)) return rc;
     if (!d_dbs || !d_idx || !d_recs) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
     if (((uintptr_t)d_dbs | (uintptr_t)d_recs) % 16 != 0 || (uintptr_t)d_idx % 8 != 0)
         return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
@@ -1037,11 +1075,29 @@ int dpf_pir_db_gather_sliced_wide_dev(int device, const uint8_t* d_dbs, uint64_t
     return DPF_OK;
 }
 
+int dpf_pir_db_update_sliced_any_dev(int device, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, const uint64_t* d_idx,
+                                     const uint8_t* d_recs, size_t n, void* stream) {
+    if (int rc = check_update_bufs(rec_bytes, d_dbs, d_idx, d_recs, true)) return rc;
+    if (n == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_update_sliced(d_dbs, nrec, rec_bytes, d_idx, d_recs, n, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_pir_db_gather_sliced_any_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                     const uint64_t* d_idx, size_t n, uint8_t* d_out, void* stream) {
+    if (int rc = check_update_bufs(rec_bytes, d_dbs, d_idx, d_out, true)) return rc;
+    if (n == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_gather_sliced(d_dbs, nrec, rec_bytes, d_idx, n, d_out, (hipStream_t)stream));
+    return DPF_OK;
+}
+
 // Private writes (the dual of the fold): every argument is checked before
 // any device call, in the order rec_bytes, bits_stride, nrec, null, alignment.
 static int check_scatter_bufs(size_t rec_bytes, const void* d_bits, size_t bits_stride, uint64_t nrec,
-                              const void* d_msgs, const void* d_db) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+                              const void* d_msgs, const void* d_db, bool any = false) {
+    if (int rc = check_rec_bytes(rec_bytes, any)) return rc;
     if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
     if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
     if (!d_bits || !d_msgs || !d_db) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
@@ -1051,8 +1107,9 @@ static int check_scatter_bufs(size_t rec_bytes, const void* d_bits, size_t bits_
 }
 
 static int xor_scatter(bool sliced, int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
-                       const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec, size_t rec_bytes, void* stream) {
-    if (int rc = check_scatter_bufs(rec_bytes, d_bits, bits_stride, nrec, d_msgs, d_db)) return rc;
+                       const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec, size_t rec_bytes, void* stream,
+                       bool any = false) {
+    if (int rc = check_scatter_bufs(rec_bytes, d_bits, bits_stride, nrec, d_msgs, d_db, any)) return rc;
     if (nkeys == 0 || nrec == 0) return DPF_OK;
     DeviceGuard g(device);
     CuScope cus(stream);
@@ -1072,13 +1129,19 @@ int dpf_xor_scatter_sliced_wide_dev(int device, const uint8_t* d_bits, size_t bi
     return xor_scatter(true, device, d_bits, bits_stride, nkeys, d_msgs, d_dbs, nrec, rec_bytes, stream);
 }
 
+int dpf_xor_scatter_sliced_any_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                   const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                   void* stream) {
+    return xor_scatter(true, device, d_bits, bits_stride, nkeys, d_msgs, d_dbs, nrec, rec_bytes, stream, true);
+}
+
 // The private write of the two *_dev entries below: the subtree EvalFull into
 // the workspace (pir_answer's layout, always the split path), then the
 // scatter of the messages over the DB.
 static int pir_write(bool sliced, int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
                      uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_db, uint64_t nrec,
-                     size_t rec_bytes, void* d_work, void* stream) {
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+                     size_t rec_bytes, void* d_work, void* stream, bool any = false) {
+    if (int rc = check_rec_bytes(rec_bytes, any)) return rc;
     if (int rc = check_key(klen, logN)) return rc;
     const uint32_t stop = stop_of(logN);
     if (!dpfh::prefix_ok(prefix_bits, prefix, stop)) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
@@ -1114,6 +1177,13 @@ int dpf_pir_write_sliced_wide_dev(int device, const uint8_t* d_keys, size_t klen
                      stream);
 }
 
+int dpf_pir_write_sliced_any_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                                 uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_dbs,
+                                 uint64_t nrec, size_t rec_bytes, void* d_work, void* stream) {
+    return pir_write(true, device, d_keys, klen, nkeys, logN, prefix_bits, prefix, d_msgs, d_dbs, nrec, rec_bytes, d_work,
+                     stream, true);
+}
+
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
 
 int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
@@ -1126,7 +1196,8 @@ int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
 struct PirDb {
     uint32_t logN = 0, pbits = 0;
     uint64_t nrec = 0;
-    size_t rec_bytes = 32;
+    size_t rec_bytes = 32;         // the caller's record width
+    size_t w4 = 32;                // bytes per record on the device: rec_bytes rounded up to a multiple of 4, pad zero
     bool sliced = true;            // shards in the bit-sliced layout (the matrix-core fold)
     DevList devs;                  // per shard: its device
     std::vector<void*> shard;      // per device: its DB slice
@@ -1148,11 +1219,33 @@ size_t dpf_pir_db_rec_bytes(void* handle) { return handle ? ((PirDb*)handle)->re
 // Upload chunk of a sliced shard: whole super-groups, at most this many bytes.
 constexpr uint64_t kPirUploadChunk = 256ull << 20;
 
-int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
-                           void** handle) {
+// Rows of `w` bytes between a tight host array [n][w] and device rows of
+// `pitch` >= w bytes (the handle's padded records), in either direction.
+static hipError_t copy_rows_up(void* dev, size_t pitch, const uint8_t* host, size_t w, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (w == pitch) return hipMemcpyAsync(dev, host, n * w, hipMemcpyHostToDevice, st);
+    if (hipError_t e = hipMemsetAsync(dev, 0, n * pitch, st); e != hipSuccess) return e;   // the pad bytes are zero
+    return hipMemcpy2DAsync(dev, pitch, host, w, w, n, hipMemcpyHostToDevice, st);
+}
+static hipError_t copy_rows_down(uint8_t* host, const void* dev, size_t pitch, size_t w, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (w == pitch) return hipMemcpyAsync(host, dev, n * w, hipMemcpyDeviceToHost, st);
+    return hipMemcpy2DAsync(host, w, dev, pitch, w, n, hipMemcpyDeviceToHost, st);
+}
+
+// any: dpf_pir_db_create_any (every width from 1 byte; shards at w4 bytes per
+// record); else dpf_pir_db_create_wide's rule.
+static int pir_db_create(const uint8_t* db, uint64_t nrec, size_t caller_bytes, uint32_t logN, int ngpus, void** handle,
+                         bool any) {
     if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
     *handle = nullptr;
-    if (int rc = check_rec_bytes(rec_bytes)) return rc;
+    if (any) {
+        if (caller_bytes == 0 || caller_bytes > DPF_PIR_MAX_REC_BYTES)
+            return fail(DPF_ERR_PARAM, "dpf: rec_bytes must be 1 .. DPF_PIR_MAX_REC_BYTES");
+    } else if (int rc = check_rec_bytes(caller_bytes)) {
+        return rc;
+    }
+    const size_t rec_bytes = (caller_bytes + 3) & ~(size_t)3;   // on the device
     if (logN > 63 || (logN < 64 && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: DB larger than 2^logN");
     int have = 0;
     const DevList devs = pick_devs(0, &have);
@@ -1165,20 +1258,23 @@ int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, u
     h->logN = logN;
     h->pbits = pb;
     h->nrec = nrec;
-    h->rec_bytes = rec_bytes;
+    h->rec_bytes = caller_bytes;
+    h->w4 = rec_bytes;
     // DPF_PIR_FOLD=lds keeps the row-major shards and the LDS fold (A/B runs).
     static const bool lds = [] {
         const char* e = getenv("DPF_PIR_FOLD");
         return e && e[0] == 'l';
     }();
     h->sliced = !lds;
+    if (lds && caller_bytes % 32 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: row-major shards (DPF_PIR_FOLD=lds) take multiples of 32 bytes only");
     const uint64_t slice = 1ull << (logN - pb);
     for (int g = 0; g < want; ++g) {
         const uint64_t lo = std::min<uint64_t>(nrec, (uint64_t)g * slice);
         const uint64_t hi = std::min<uint64_t>(nrec, lo + slice);
         DeviceGuard gd(devs[(size_t)g]->id);
         void* p = nullptr;
-        const size_t bytes = h->sliced ? dpf_pir_db_sliced_size_wide(hi - lo, rec_bytes)
+        const size_t bytes = h->sliced ? dpf_pir_db_sliced_size_any(hi - lo, rec_bytes)
                                        : std::max<uint64_t>(hi - lo, 1) * rec_bytes;
         if (hipMalloc(&p, bytes) != hipSuccess) return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
         h->devs.push_back(devs[(size_t)g]);     // ~PirDb frees what was allocated so far
@@ -1201,7 +1297,7 @@ int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, u
         bool ok = true;
         for (uint64_t r0 = lo; ok && r0 < hi; r0 += chunk) {
             const uint64_t n = std::min<uint64_t>(chunk, hi - r0);
-            ok = hipMemcpy(tmp, db + r0 * rec_bytes, n * rec_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+            ok = copy_rows_up(tmp, rec_bytes, db + r0 * caller_bytes, caller_bytes, n, nullptr) == hipSuccess &&
                  dpfk::launch_slice_db((const uint8_t*)tmp, n, rec_bytes, (uint8_t*)p + (r0 - lo) * rec_bytes,
                                        nullptr) == hipSuccess &&
                  hipDeviceSynchronize() == hipSuccess;   // tmp is reused by the next chunk
@@ -1213,12 +1309,21 @@ int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, u
     return DPF_OK;
 }
 
+int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
+                           void** handle) {
+    return pir_db_create(db, nrec, rec_bytes, logN, ngpus, handle, false);
+}
+
+int dpf_pir_db_create_any(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle) {
+    return pir_db_create(db, nrec, rec_bytes, logN, ngpus, handle, true);
+}
+
 int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, uint8_t* ans) {
     PirDb* h = (PirDb*)handle;
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
     if (int rc = check_key(klen, h->logN)) return rc;
     const int g = (int)h->shard.size();
-    const size_t rb = h->rec_bytes;
+    const size_t rb = h->rec_bytes, w4 = h->w4;
     std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * rb));
     int rc = shard((size_t)g, g, [&](int dev, size_t lo, size_t hi) {
         (void)hi;
@@ -1227,14 +1332,14 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
         DeviceGuard gd(d.id);
         HIP_TRY(d.keys.ensure(std::max<size_t>(1, nkeys * klen)));
         HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
-        HIP_TRY(d.out.ensure(std::max<size_t>(32, nkeys * rb)));
+        HIP_TRY(d.out.ensure(std::max<size_t>(32, nkeys * w4)));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
-        // (rec_bytes == 32: the _wide entries are the 32-byte entries.)
-        int r = (h->sliced ? dpf_pir_answer_sliced_wide_dev : dpf_pir_answer_wide_dev)(
+        // (Row-major shards are multiples of 32 bytes; sliced ones any multiple of 4.)
+        int r = (h->sliced ? dpf_pir_answer_sliced_any_dev : dpf_pir_answer_wide_dev)(
             d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)h->shard[lo],
-            h->shard_n[lo], rb, (uint8_t*)d.out.p, d.work.p, d.st);
+            h->shard_n[lo], w4, (uint8_t*)d.out.p, d.work.p, d.st);
         if (r) return r;
-        HIP_TRY(hipMemcpyAsync(part[lo].data(), d.out.p, nkeys * rb, hipMemcpyDeviceToHost, d.st));
+        HIP_TRY(copy_rows_down(part[lo].data(), d.out.p, w4, rb, nkeys, d.st));
         HIP_TRY(hipStreamSynchronize(d.st));
         return DPF_OK;
     });
@@ -1254,7 +1359,7 @@ uint64_t dpf_pir_db_nrec(void* handle) { return handle ? ((PirDb*)handle)->nrec 
 // before or after the chunk, never in between.
 static int pir_update_chunk(PirDb* h, size_t s, const dpfh::PirUpdatePlan& plan, size_t a, size_t b,
                             const uint8_t* recs, uint8_t* out, std::vector<uint8_t>& host) {
-    const size_t rb = h->rec_bytes, m = b - a;
+    const size_t rb = h->rec_bytes, w4 = h->w4, m = b - a;
     Dev& d = *h->devs[s];
     uint8_t* db = (uint8_t*)h->shard[s];
     const uint64_t nrec = h->shard_n[s];
@@ -1274,17 +1379,17 @@ static int pir_update_chunk(PirDb* h, size_t s, const dpfh::PirUpdatePlan& plan,
     std::lock_guard<std::mutex> lk(d.mu);
     DeviceGuard gd(d.id);
     HIP_TRY(d.xs.ensure(m * 8));
-    HIP_TRY(d.out.ensure(m * rb));
+    HIP_TRY(d.out.ensure(m * w4));
     const uint64_t* d_idx = (const uint64_t*)d.xs.p;
     HIP_TRY(hipMemcpyAsync(d.xs.p, plan.local.data() + a, m * 8, hipMemcpyHostToDevice, d.st));
     if (recs) {
-        HIP_TRY(hipMemcpyAsync(d.out.p, stage, m * rb, hipMemcpyHostToDevice, d.st));
-        HIP_TRY((h->sliced ? dpfk::launch_update_sliced : dpfk::launch_update_rows)(db, nrec, rb, d_idx,
+        HIP_TRY(copy_rows_up(d.out.p, w4, stage, rb, m, d.st));
+        HIP_TRY((h->sliced ? dpfk::launch_update_sliced : dpfk::launch_update_rows)(db, nrec, w4, d_idx,
                                                                                     (const uint8_t*)d.out.p, m, d.st));
     } else {
-        HIP_TRY((h->sliced ? dpfk::launch_gather_sliced : dpfk::launch_gather_rows)(db, nrec, rb, d_idx, m,
+        HIP_TRY((h->sliced ? dpfk::launch_gather_sliced : dpfk::launch_gather_rows)(db, nrec, w4, d_idx, m,
                                                                                     (uint8_t*)d.out.p, d.st));
-        HIP_TRY(hipMemcpyAsync(stage, d.out.p, m * rb, hipMemcpyDeviceToHost, d.st));
+        HIP_TRY(copy_rows_down(stage, d.out.p, w4, rb, m, d.st));
     }
     HIP_TRY(hipStreamSynchronize(d.st));
     if (d.out.cap > 2 * kStageBytes) d.out.release();   // a large chunk's staging is not kept
@@ -1304,7 +1409,7 @@ static int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const
     dpfh::PirUpdatePlan plan;
     if (!dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan))
         return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
-    const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->rec_bytes);
+    const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->w4);
     std::vector<uint8_t> host;
     for (size_t s = 0; s + 1 < plan.shard_off.size(); ++s)
         for (size_t a = plan.shard_off[s]; a < plan.shard_off[s + 1]; a += chunk)
@@ -1332,7 +1437,7 @@ int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkey
     if (nkeys == 0) return DPF_OK;
     if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
     const int g = (int)h->shard.size();
-    const size_t rb = h->rec_bytes;
+    const size_t rb = h->rec_bytes, w4 = h->w4;
     return shard((size_t)g, g, [&](int dev, size_t lo, size_t hi) {
         (void)hi;
         if (h->shard_n[lo] == 0) return (int)DPF_OK;
@@ -1341,12 +1446,12 @@ int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkey
         DeviceGuard gd(d.id);
         HIP_TRY(d.keys.ensure(nkeys * klen));
         HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
-        HIP_TRY(d.out.ensure(nkeys * rb));
+        HIP_TRY(d.out.ensure(nkeys * w4));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
-        HIP_TRY(hipMemcpyAsync(d.out.p, msgs, nkeys * rb, hipMemcpyHostToDevice, d.st));
-        int r = (h->sliced ? dpf_pir_write_sliced_wide_dev : dpf_pir_write_wide_dev)(
+        HIP_TRY(copy_rows_up(d.out.p, w4, msgs, rb, nkeys, d.st));   // zero pad bytes: the DB's stay zero
+        int r = (h->sliced ? dpf_pir_write_sliced_any_dev : dpf_pir_write_wide_dev)(
             d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)d.out.p,
-            (uint8_t*)h->shard[lo], h->shard_n[lo], rb, d.work.p, d.st);
+            (uint8_t*)h->shard[lo], h->shard_n[lo], w4, d.work.p, d.st);
         if (r) return r;
         HIP_TRY(hipStreamSynchronize(d.st));
         return (int)DPF_OK;

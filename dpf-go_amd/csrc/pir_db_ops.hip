@@ -53,9 +53,16 @@ namespace dpfk {
 // from i < n: no access leaves the buffers.  Sparse updates are bound by the
 // three dependent round trips of a tile (index, tile and record loads), so
 // the kernel is held to 8 waves per SIMD (measurements: profiles/pir_update).
+//
+// Records of any width (ntiles = rec_bytes / 4 words): a super-group is
+// 32 ntiles rows, thread t of column c has a row only if 256 c + t is below
+// that, and a wave's two record words are read as one uint2 only where the
+// record is an even number of words (then rows of recs are 8-byte aligned and
+// word 8 c + 2 w + 1 exists whenever 8 c + 2 w does).  Threads without a row
+// still take part in the ballots; they load and store nothing.
 constexpr uint32_t kUpdSeqMin = 16;   // consecutive updates of a batch from which the ballot form is cheaper
 __global__ __launch_bounds__(256, 8) void k_update_sliced(uint4* __restrict__ dbs, uint64_t nrec, uint32_t ncols,
-                                                        const uint64_t* __restrict__ idx,
+                                                        uint32_t ntiles, const uint64_t* __restrict__ idx,
                                                         const uint32_t* __restrict__ recs, uint64_t n, uint64_t i_base,
                                                         uint32_t K, uint32_t nchunks) {
     const uint32_t c = blockIdx.x % ncols;
@@ -75,14 +82,18 @@ __global__ __launch_bounds__(256, 8) void k_update_sliced(uint4* __restrict__ db
         heads = __builtin_amdgcn_ballot_w64(head);
     }
     const uint32_t w = t >> 6;                  // bit positions 64 w .. 64 w + 63: words 2 w, 2 w + 1 of the column
-    const uint2* recs2 = reinterpret_cast<const uint2*>(recs);
+    const uint32_t w0i = 8 * c + 2 * w;          // this wave's first word of a record
+    const uint32_t nwv = w0i >= ntiles ? 0u : ntiles - w0i < 2 ? 1u : 2u;
+    const bool pair = (ntiles & 1) == 0;
+    const bool live = 256u * c + t < 32u * ntiles;
     while (heads) {
         const uint32_t u = (uint32_t)__builtin_ctzll(heads);
         heads &= heads - 1;
         uint64_t i = i0 + u;
         const uint64_t S = idx[i] >> 8;
-        uint4* row = &dbs[((S * ncols + c) * 256 + t) * 2];
-        const uint4 a = row[0], b = row[1];
+        uint4* row = &dbs[(S * 32 * ntiles + 256u * c + t) * 2];
+        uint4 a = make_uint4(0, 0, 0, 0), b = a;
+        if (live) a = row[0], b = row[1];
         uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         for (;;) {
             // Entries i .. i + 63, one per lane: how many continue the run,
@@ -92,7 +103,15 @@ __global__ __launch_bounds__(256, 8) void k_update_sliced(uint4* __restrict__ db
             if (il < n) v = idx[il];
             const bool in = v < nrec && (v >> 8) == S;
             uint2 wv = make_uint2(0, 0);
-            if (in) wv = recs2[(il * ncols + c) * 4 + w];
+            if (in && nwv) {
+                const uint32_t* rw = recs + il * ntiles + w0i;
+                if (pair) {
+                    wv = *reinterpret_cast<const uint2*>(rw);
+                } else {
+                    wv.x = rw[0];
+                    if (nwv > 1) wv.y = rw[1];
+                }
+            }
             const uint64_t m = __builtin_amdgcn_ballot_w64(in);
             const uint32_t cnt = ~m ? (uint32_t)__builtin_ctzll(~m) : 64u;
             const uint32_t lo = (uint32_t)v & 255u;
@@ -135,28 +154,29 @@ __global__ __launch_bounds__(256, 8) void k_update_sliced(uint4* __restrict__ db
             if (cnt < 64) break;
             i += 64;
         }
-        row[0] = make_uint4(x[0], x[1], x[2], x[3]);
-        row[1] = make_uint4(x[4], x[5], x[6], x[7]);
+        if (live) {
+            row[0] = make_uint4(x[0], x[1], x[2], x[3]);
+            row[1] = make_uint4(x[4], x[5], x[6], x[7]);
+        }
     }
 }
 
 // Record idx[i] of the sliced DB in row-major form (zeros for idx[i] >= nrec):
-// one thread per output word (i, c, wd), bit b of it = bit j of
-// dbs[S][c][32 wd + b][g].  Not a hot path: 32 loads of 4 bytes per word.
-__global__ __launch_bounds__(256) void k_gather_sliced(const uint32_t* __restrict__ dbs, uint64_t nrec, uint32_t ncols,
+// one thread per output word (i, wd) of the record's ntiles words (any width:
+// one word per bit tile), bit b of it = bit j of row 32 wd + b, group g of
+// super-group S.  Not a hot path: 32 loads of 4 bytes per word.
+__global__ __launch_bounds__(256) void k_gather_sliced(const uint32_t* __restrict__ dbs, uint64_t nrec, uint32_t ntiles,
                                                         const uint64_t* __restrict__ idx, uint64_t nwords,
                                                         uint32_t* __restrict__ out) {
     const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (tid >= nwords) return;
-    const uint32_t wd = (uint32_t)(tid & 7);
-    const uint64_t ic = tid >> 3;
-    const uint32_t c = (uint32_t)(ic % ncols);
-    const uint64_t r = idx[ic / ncols];
+    const uint32_t wd = (uint32_t)(tid % ntiles);
+    const uint64_t r = idx[tid / ntiles];
     uint32_t o = 0;
     if (r < nrec) {
         const uint64_t S = r >> 8;
         const uint32_t g = ((uint32_t)r & 255u) >> 5, j = (uint32_t)r & 31u;
-        const uint32_t* p = dbs + ((S * ncols + c) * 256 + 32 * wd) * 8 + g;
+        const uint32_t* p = dbs + ((S * ntiles + wd) * 32) * 8 + g;
 #pragma unroll 8
         for (uint32_t b = 0; b < 32; ++b) o |= ((p[8 * b] >> j) & 1u) << b;
     }
@@ -191,13 +211,13 @@ using dpfh::rec_bytes_ok;
 
 hipError_t launch_update_sliced(uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx,
                                 const uint8_t* recs, uint64_t n, hipStream_t st) {
-    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
     if (n == 0 || nrec == 0) return hipSuccess;
-    const uint64_t C = rec_bytes / 32;
+    const uint64_t C = dpfh::rec_cols(rec_bytes);
     const dpfh::UpdatePlan p = dpfh::plan_update_sliced(n, (nrec + 255) / 256, C);
     return dpfh::for_each_span(n, p.span, [&](uint64_t i0, uint64_t m) {
         hipLaunchKernelGGL(k_update_sliced, dim3((uint32_t)p.grid(m, C)), dim3(256), 0, st,
-                           reinterpret_cast<uint4*>(dbs), nrec, (uint32_t)C, idx,
+                           reinterpret_cast<uint4*>(dbs), nrec, (uint32_t)C, dpfh::rec_tiles(rec_bytes), idx,
                            reinterpret_cast<const uint32_t*>(recs), n, i0, p.K, (uint32_t)p.chunks(m));
         return hipGetLastError();
     });
@@ -215,11 +235,11 @@ static hipError_t for_record_chunks(uint64_t n, uint64_t per_rec, F fn) {
 
 hipError_t launch_gather_sliced(const uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
                                 uint8_t* out, hipStream_t st) {
-    if (!rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
-    const uint64_t C = rec_bytes / 32;
-    return for_record_chunks(n, 8 * C, [&](uint64_t i0, uint64_t, uint64_t threads) {
+    if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
+    const uint64_t T = dpfh::rec_tiles(rec_bytes);
+    return for_record_chunks(n, T, [&](uint64_t i0, uint64_t, uint64_t threads) {
         hipLaunchKernelGGL(k_gather_sliced, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const uint32_t*>(dbs), nrec, (uint32_t)C, idx + i0, threads,
+                           reinterpret_cast<const uint32_t*>(dbs), nrec, (uint32_t)T, idx + i0, threads,
                            reinterpret_cast<uint32_t*>(out + i0 * rec_bytes));
     });
 }
@@ -273,6 +293,14 @@ hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_byt
 // a key's row (wpk) are not read.  The next tile's loads are issued before the
 // current one's arithmetic.  Each tile is read once and written once by one
 // workgroup: no atomics, no scratch.
+//
+// Records of any width (ntiles = rec_bytes / 4 words): a super-group is
+// 64 ntiles uint4, a thread's uint4 (c0 + ci) 512 + t + 256 sl exists only
+// below that (no load, no store, zero message bits otherwise), and the
+// messages, whose rows are then only 4-byte aligned, are staged word by word.
+// FULL: the record is whole columns (a multiple of 32 bytes); the row guards
+// become the column test and the kernel is the one from before records of any
+// width (with the guards in, 32- and 64-byte records measured 1.5-2.5 % slower).
 constexpr int kScatterSB = 4;                        // super-groups per staging round
 constexpr int kScatterKT = (int)dpfh::kScatterKeyTile;
 static_assert(dpfh::kScatterMaxCols == 4, "k_scatter_sliced is instantiated for 1 .. 4 columns");
@@ -283,10 +311,12 @@ __device__ __forceinline__ uint32_t scatter_live(uint64_t ww, uint64_t nrec) {
     return nrec >= r0 + 32 ? ~0u : nrec <= r0 ? 0u : (1u << (uint32_t)(nrec - r0)) - 1u;
 }
 
-template <int CG>
-__global__ __launch_bounds__(256) void k_scatter_sliced(const uint32_t* __restrict__ bits, uint64_t wpk,
+// (Held to the waves per SIMD that each CG had before the row guards: 5, 4, 5, 4.)
+template <int CG, bool FULL>
+__global__ __launch_bounds__(256, CG == 2 || CG == 4 ? 4 : 5) void k_scatter_sliced(
+                                                        const uint32_t* __restrict__ bits, uint64_t wpk,
                                                         uint4* __restrict__ dbs, uint64_t nrec, uint64_t nsg,
-                                                        uint32_t ncols, const uint4* __restrict__ msgs, uint32_t rec_u4,
+                                                        uint32_t ncols, const uint4* __restrict__ msgs, uint32_t ntiles,
                                                         uint32_t kt, uint64_t run, uint32_t ncg, uint64_t u0) {
     __shared__ uint4 sel[kScatterKT][kScatterSB][2];            // 8 KiB; first the messages [kt][2 CG]
     static_assert(sizeof(sel) >= (size_t)kScatterKT * 2 * CG * sizeof(uint4), "the staged messages fit");
@@ -301,9 +331,18 @@ __global__ __launch_bounds__(256) void k_scatter_sliced(const uint32_t* __restri
     uint32_t mb[CG][2][2];                                     // [column][slot][key word]
     {
         uint4* mst = &sel[0][0][0];
-        for (uint32_t i = t; i < kt * 2 * CG; i += 256) {
-            const uint32_t k = i / (2 * CG), q = 2 * c0 + i % (2 * CG);
-            mst[i] = q < 2 * ncols ? msgs[(uint64_t)k * rec_u4 + q] : make_uint4(0, 0, 0, 0);
+        if (FULL) {
+            for (uint32_t i = t; i < kt * 2 * CG; i += 256) {
+                const uint32_t k = i / (2 * CG), q = 2 * c0 + i % (2 * CG);
+                mst[i] = q < 2 * ncols ? msgs[(uint64_t)k * (ntiles / 4) + q] : make_uint4(0, 0, 0, 0);
+            }
+        } else {
+            uint32_t* mw = reinterpret_cast<uint32_t*>(mst);
+            const uint32_t* msgw = reinterpret_cast<const uint32_t*>(msgs);
+            for (uint32_t i = t; i < kt * 8 * CG; i += 256) {
+                const uint32_t k = i / (8 * CG), q = 8 * c0 + i % (8 * CG);
+                mw[i] = q < ntiles ? msgw[(uint64_t)k * ntiles + q] : 0u;
+            }
         }
         __syncthreads();
         const uint8_t* mbytes = reinterpret_cast<const uint8_t*>(mst);
@@ -323,14 +362,16 @@ __global__ __launch_bounds__(256) void k_scatter_sliced(const uint32_t* __restri
             }
     }
 
-    auto tile = [&](uint64_t S, int ci) { return &dbs[((S * ncols + c0 + ci) * 256) * 2 + t]; };
+    const uint32_t sg_u4 = 64 * ntiles;                        // uint4 per super-group
+    auto tile = [&](uint64_t S, int ci) { return &dbs[S * sg_u4 + (c0 + ci) * 512 + t]; };
+    const uint32_t left = sg_u4 > c0 * 512 + t ? sg_u4 - (c0 * 512 + t) : 0;   // uint4 from this thread's first to the end
+    auto have = [&](int ci, int sl) { return FULL ? c0 + ci < ncols : (uint32_t)(ci * 512 + 256 * sl) < left; };
     auto load = [&](uint64_t S, uint4 (&x)[CG][2]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int ci = 0; ci < CG; ++ci)
-            if (c0 + ci < ncols) {
-                x[ci][0] = tile(S, ci)[0];
-                x[ci][1] = tile(S, ci)[256];
-            }
+        for (int ci = 0; ci < CG; ++ci) {
+            if (have(ci, 0)) x[ci][0] = tile(S, ci)[0];
+            if (have(ci, 1)) x[ci][1] = tile(S, ci)[256];
+        }
     };
     uint4 cur[CG][2] = {}, nxt[CG][2] = {};
     load(s0, cur);
@@ -374,11 +415,10 @@ __global__ __launch_bounds__(256) void k_scatter_sliced(const uint32_t* __restri
                 }
             }
 #pragma unroll
-            for (int ci = 0; ci < CG; ++ci)
-                if (c0 + ci < ncols) {
-                    tile(S, ci)[0] = cur[ci][0];
-                    tile(S, ci)[256] = cur[ci][1];
-                }
+            for (int ci = 0; ci < CG; ++ci) {
+                if (have(ci, 0)) tile(S, ci)[0] = cur[ci][0];
+                if (have(ci, 1)) tile(S, ci)[256] = cur[ci][1];
+            }
 #pragma unroll
             for (int ci = 0; ci < CG; ++ci) {
                 cur[ci][0] = nxt[ci][0];
@@ -419,12 +459,13 @@ __global__ __launch_bounds__(256) void k_xor_scatter_rows(const uint32_t* __rest
 template <int CG>
 static hipError_t scatter_sliced_cg(const dpfh::ScatterPlan& p, const uint32_t* bits, uint64_t wpk, uint8_t* dbs,
                                     uint64_t nrec, uint64_t rec_bytes, const uint8_t* msgs, hipStream_t st) {
+    const auto kernel = rec_bytes % 32 == 0 ? k_scatter_sliced<CG, true> : k_scatter_sliced<CG, false>;
     for (uint64_t tile = 0; tile < p.key_tiles(); ++tile) {
         const dpfh::ScatterUnit k = p.unit(tile, 0);
         for (uint64_t l = 0; l < p.launches(); ++l) {
-            hipLaunchKernelGGL(k_scatter_sliced<CG>, dim3((uint32_t)p.blocks(l)), dim3(256), 0, st, bits + k.k0 * wpk,
-                               wpk, reinterpret_cast<uint4*>(dbs), nrec, p.nsg, p.C,
-                               reinterpret_cast<const uint4*>(msgs + k.k0 * rec_bytes), (uint32_t)(rec_bytes / 16),
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)p.blocks(l)), dim3(256), 0, st, bits + k.k0 * wpk, wpk,
+                               reinterpret_cast<uint4*>(dbs), nrec, p.nsg, p.C,
+                               reinterpret_cast<const uint4*>(msgs + k.k0 * rec_bytes), dpfh::rec_tiles(rec_bytes),
                                (uint32_t)(k.k1 - k.k0), p.run, p.ncg, p.first(l));
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         }
@@ -434,10 +475,11 @@ static hipError_t scatter_sliced_cg(const dpfh::ScatterPlan& p, const uint32_t* 
 
 hipError_t launch_scatter_sliced(const uint32_t* bits, uint64_t words_per_key, uint8_t* dbs, uint64_t nrec,
                                  uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st) {
-    if (!rec_bytes_ok(rec_bytes) || words_per_key % 4 != 0 || nrec > words_per_key * 32) return hipErrorInvalidValue;
+    if (!dpfh::rec_bytes_any_ok(rec_bytes) || words_per_key % 4 != 0 || nrec > words_per_key * 32)
+        return hipErrorInvalidValue;
     if (nkeys == 0 || nrec == 0) return hipSuccess;
     const dpfh::FoldLimits lim = fold_limits();
-    const dpfh::ScatterPlan p = dpfh::plan_scatter(nrec, (uint32_t)(rec_bytes / 32), nkeys, (uint32_t)cu_count(),
+    const dpfh::ScatterPlan p = dpfh::plan_scatter(nrec, dpfh::rec_cols(rec_bytes), nkeys, (uint32_t)cu_count(),
                                                    lim.max_blocks, lim.max_sg);
     switch (p.cols) {
         case 1: return scatter_sliced_cg<1>(p, bits, words_per_key, dbs, nrec, rec_bytes, msgs, st);

@@ -58,6 +58,33 @@ inline bool rec_bytes_ok(uint64_t rec_bytes) {
     return rec_bytes != 0 && rec_bytes % 32 == 0 && rec_bytes <= kFoldMaxRecBytes;
 }
 
+// ---- records of any width over the sliced layout ---------------------------
+// The sliced kernels take every positive multiple of 4 bytes: a record is
+// T = rec_bytes / 4 bit tiles of 32 rows (bit positions) in C = ceil(T / 8)
+// columns, a super-group 32 T rows of 8 words with no padding after the last
+// one, so the last column of a record may be short (8 * rec_bytes - 256 c
+// rows) and a tile 8 c + i >= T does not exist: its rows would lie in the next
+// super-group, or past the buffer.  Multiples of 32 are T = 8 C, every tile
+// present.
+inline bool rec_bytes_any_ok(uint64_t rec_bytes) {
+    return rec_bytes != 0 && rec_bytes % 4 == 0 && rec_bytes <= kFoldMaxRecBytes;
+}
+inline uint32_t rec_tiles(uint64_t rec_bytes) { return (uint32_t)(rec_bytes / 4); }
+inline uint32_t rec_cols(uint64_t rec_bytes) { return (uint32_t)((rec_bytes + 31) / 32); }
+// Rows (bit positions) and bit tiles of column c < rec_cols().
+inline uint32_t col_rows(uint64_t rec_bytes, uint32_t c) {
+    const uint64_t left = 8 * rec_bytes - 256ull * c;
+    return (uint32_t)(left < 256 ? left : 256);
+}
+inline uint32_t col_tiles(uint64_t rec_bytes, uint32_t c) { return col_rows(rec_bytes, c) / 32; }
+inline bool tile_exists(uint64_t rec_bytes, uint64_t tile) { return tile < rec_bytes / 4; }
+inline uint64_t sg_stride_bytes(uint64_t rec_bytes) { return 256 * rec_bytes; }
+inline uint64_t sliced_bytes_any(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * sg_stride_bytes(rec_bytes); }
+// Byte offset of tile `tile` (32 rows of 8 words: 1 KiB) of super-group S.
+inline uint64_t tile_off_bytes(uint64_t rec_bytes, uint64_t S, uint64_t tile) {
+    return S * sg_stride_bytes(rec_bytes) + tile * 1024;
+}
+
 // Part slices per answer word of k_xor_parts, one atomic each: 16 for <= 256
 // partials (the PIR rank at N = 8: step 0.0733-0.0737 vs 0.0740-0.0745 ms with
 // 64, 8 in between), 64 above (one GPU, 768 partials: 0.3799-0.3802 vs
@@ -183,6 +210,11 @@ inline int fold_tile_index(uint32_t nk, int cg) {
 // slices that stay cached between batches lose.
 inline uint64_t fold_db_bytes(uint64_t nsg, uint32_t C) { return nsg * 256 * 32 * C; }
 inline bool fold_ntdb(uint64_t nsg, uint32_t C, uint64_t nt_min) { return fold_db_bytes(nsg, C) >= nt_min; }
+// The same for any width, by the bytes the DB really has.
+inline uint64_t fold_db_bytes_any(uint64_t nsg, uint64_t rec_bytes) { return nsg * sg_stride_bytes(rec_bytes); }
+inline bool fold_ntdb_any(uint64_t nsg, uint64_t rec_bytes, uint64_t nt_min) {
+    return fold_db_bytes_any(nsg, rec_bytes) >= nt_min;
+}
 
 // Workgroups per CU of a matrix-core fold launch: resident workgroups only
 // (one round), each a contiguous run of whole staged blocks.  (A fixed 4
@@ -227,6 +259,8 @@ struct SlicedFoldPlan {
     uint64_t nsg, ncg, cap, msg, gran, resident;
     uint32_t C;
     uint64_t clear_words;
+    uint64_t rec_bytes = 0;   // 0: 32 C (the plans from before records of any width)
+    uint64_t sg_bytes() const { return sg_stride_bytes(rec_bytes ? rec_bytes : 32ull * C); }
 
     // fn(const FoldLaunch&) for every launch in stream order, until one
     // returns a nonzero (error) value, which is returned.
@@ -244,7 +278,7 @@ struct SlicedFoldPlan {
                 if (want < 1) want = 1;
                 const ChunkSplit s = split_chunks(n, want, gran, xcap);
                 const bool first = g0 == 0 && S0 == 0;
-                const FoldLaunch l{g0, gy, S0, n, s.blocks, s.cpb, S0 * 8, S0 * 256 * 32 * C, first ? clear_words : 0};
+                const FoldLaunch l{g0, gy, S0, n, s.blocks, s.cpb, S0 * 8, S0 * sg_bytes(), first ? clear_words : 0};
                 if (auto e = fn(l); e != decltype(e){}) return e;
             }
         }
@@ -255,19 +289,25 @@ struct SlicedFoldPlan {
 // The answer words that the first launch of key group k0 clears: all of the
 // call's, in its first key group.
 inline uint64_t fold_clear_words(uint32_t nkeys, uint32_t C, uint32_t k0) { return k0 == 0 ? (uint64_t)nkeys * 8 * C : 0; }
+// For any width: T = rec_tiles() answer words per key, tightly packed.
+inline uint64_t fold_clear_words_any(uint32_t nkeys, uint64_t rec_bytes, uint32_t k0) {
+    return k0 == 0 ? (uint64_t)nkeys * rec_tiles(rec_bytes) : 0;
+}
 
 // k_fold_mfma with tile shape t for one key group; clear_words: fold_clear_words().
 // resident: CUs x fold_per_cu().
+// C columns (rec_cols()); rec_bytes: the record width where it is not 32 C.
 inline SlicedFoldPlan plan_fold_mfma(uint64_t nsg, uint32_t C, const FoldTile& t, FoldLimits lim, uint64_t resident,
-                                     uint64_t clear_words) {
+                                     uint64_t clear_words, uint64_t rec_bytes = 0) {
     const uint64_t sg = (uint64_t)t.SG, msg = lim.max_sg / sg * sg > 0 ? lim.max_sg / sg * sg : sg;
-    return {nsg, C / (uint32_t)t.CG, lim.max_blocks, msg, sg, resident, C, clear_words};
+    return {nsg, C / (uint32_t)t.CG, lim.max_blocks, msg, sg, resident, C, clear_words, rec_bytes};
 }
 // k_fold_sliced_direct (one key): a column per grid row, runs of whole pairs
 // of super-groups, 8 workgroups per CU, one pass (XOR accumulators: no bound
 // on a run).
-inline SlicedFoldPlan plan_fold_sliced_direct(uint64_t nsg, uint32_t C, FoldLimits lim, uint64_t cus) {
-    return {nsg, C, lim.max_blocks, nsg, 2, cus * 8, C, 8ull * C};
+inline SlicedFoldPlan plan_fold_sliced_direct(uint64_t nsg, uint32_t C, FoldLimits lim, uint64_t cus,
+                                              uint64_t rec_bytes = 0) {
+    return {nsg, C, lim.max_blocks, nsg, 2, cus * 8, C, rec_bytes ? (uint64_t)rec_tiles(rec_bytes) : 8ull * C, rec_bytes};
 }
 
 // ---- grid chunking of the maintenance launches -----------------------------
@@ -279,7 +319,8 @@ auto for_each_span(uint64_t n, uint64_t per, F fn) -> decltype(fn(uint64_t{}, ui
         if (auto e = fn(i0, n - i0 < per ? n - i0 : per); e != decltype(e){}) return e;
     return {};
 }
-// k_slice_db: one workgroup per (super-group, column), at most 2^30 per launch.
+// k_slice_db: one workgroup per (super-group, column), at most 2^30 per launch
+// (C = rec_cols() for any width).
 inline uint64_t slice_db_span(uint64_t C) { return (1ull << 30) / C; }
 // Kernels of per_rec threads per record in workgroups of 256: records per
 // launch, whole records and at most 2^38 threads (2^30 workgroups).

@@ -88,11 +88,22 @@ namespace dpfk {
 // block, columns per workgroup, nontemporal DB loads, and the waves per SIMD
 // the shape is compiled for (its register budget).  cg0: first column group
 // of the launch.
-template <int MT, int NT, int SG, int CG, bool NTDB, int WPE>
+//
+// Records of any width (a multiple of 4 bytes): a record is T = rec_bytes / 4
+// bit tiles, a super-group 32 T rows with the next one directly behind, and
+// the last column may have fewer than 8 tiles.  A wave's tile 8 col + w NT + j
+// >= T does not exist (its rows would be the next super-group's, or past the
+// buffer at the last one): no load, no answer word; a wave none of whose tiles
+// exists only helps staging the selection rows.  Tile t, row r of super-group
+// S is uint4 ((S T + t) 32 + r) 2 + h, which for T = 8 C is the form above.
+// FULL: the record is whole columns (T = 8 C, a multiple of 32 bytes), every
+// tile exists and the guards fold away: the kernel from before records of any
+// width (with the guards in, 64-byte records measured 2 % slower at 64 keys).
+template <int MT, int NT, int SG, int CG, bool NTDB, int WPE, bool FULL>
 __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
     const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
     uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
-    uint64_t wlim, uint32_t ncols, uint32_t cg0) {
+    uint64_t wlim, uint32_t ntiles, uint32_t cg0) {
     constexpr int NS = 8 / NT;                                 // bit slices of a column
     constexpr int NW = NS * CG;
     constexpr bool SC = NT < MT;                               // the selection side takes the cheap expansion
@@ -106,6 +117,12 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t w = wv % NS, cw = wv / NS;                   // bit slice, column of the group
     const uint64_t col = (uint64_t)(cg0 + blockIdx.y) * CG + cw;
+    const uint64_t tile0 = 8 * col + w * NT;                    // this wave's first bit tile
+    const uint32_t nt =                                         // how many of its NT tiles the record has
+        FULL ? (uint32_t)NT
+             : __builtin_amdgcn_readfirstlane(tile0 >= ntiles               ? 0u
+                                              : ntiles - tile0 < (uint64_t)NT ? (uint32_t)(ntiles - tile0)
+                                                                              : (uint32_t)NT);
     const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
     const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
     if (s0 >= s1) return;                                       // uniform over the workgroup
@@ -127,14 +144,17 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
             if (p < (uint32_t)kPieces) *reinterpret_cast<uint4*>(&s_sel[(p / (2 * SG)) * kRow + 4 * (p % (2 * SG))]) = v[i];
         }
     };
-    // DB pieces of a whole block (clamped past the range; never folded).
+    // DB pieces of a whole block (clamped past the range; never folded).  A
+    // tile the record does not have is not loaded: zeros.
     auto load_db = [&](uint64_t sb, uint4 (&B)[SG][NT]) __attribute__((always_inline)) {
 #pragma unroll
         for (int sl = 0; sl < SG; ++sl) {
             const uint64_t S = sb + sl < s1 ? sb + sl : s1 - 1;
 #pragma unroll
-            for (int j = 0; j < NT; ++j)
-                B[sl][j] = fold_ld<NTDB>(&dbs[((S * ncols + col) * 256 + 32u * (w * NT + j) + r) * 2 + h]);
+            for (int j = 0; j < NT; ++j) {
+                B[sl][j] = make_uint4(0, 0, 0, 0);
+                if ((uint32_t)j < nt) B[sl][j] = fold_ld<NTDB>(&dbs[((S * ntiles + tile0 + j) * 32 + r) * 2 + h]);
+            }
         }
     };
     fold_v16f acc[MT][NT];
@@ -181,7 +201,7 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
         const uint64_t n = s1 - sb;
 #pragma unroll
         for (int sl = 0; sl < SG; ++sl)
-            if ((uint64_t)sl < n) fold_sg(sl, Bc[sl]);
+            if ((uint64_t)sl < n && nt != 0) fold_sg(sl, Bc[sl]);
     };
     uint64_t sb = s0;
     for (; sb + SG < s1; sb += 2 * SG) {
@@ -205,7 +225,7 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
                 out = l == row0 ? (uint32_t)b : out;
                 out = l == row0 + 4 ? (uint32_t)(b >> 32) : out;
             }
-            if (l < 32)
+            if (l < 32 && (uint32_t)j < nt)
                 parts[((uint64_t)blockIdx.x * pkeys + 32 * m + l) * pwords + (blockIdx.y * CG + cw) * 8 + w * NT + j] = out;
         }
 }
@@ -213,22 +233,35 @@ __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
 // The sliced layout (above) from a row-major DB of 32 C-byte records.
 // Workgroup b = (super-group S, column c) = (b / C, b % C); its 4 waves take
 // 64 records each: lane l holds the column's 8 words of record l and one
-// ballot per bit position transposes 32 x 32 bits.
+// ballot per bit position transposes 32 x 32 bits.  Any width: a record is
+// ntiles words, column c has nw = min(8, ntiles - 8 c) of them, and only a
+// record of whole columns (ntiles % 8 == 0: a multiple of 32 bytes) is read by
+// 16-byte loads; other rows are only 4-byte aligned.
 __global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, uint64_t nrec, uint32_t ncols,
-                                                   uint32_t* __restrict__ dbs) {
+                                                   uint32_t ntiles, uint32_t* __restrict__ dbs) {
     const uint64_t S = blockIdx.x / ncols;
     const uint32_t c = blockIdx.x % ncols;
     const uint32_t l = threadIdx.x & 63, wq = threadIdx.x >> 6;
     const uint64_t rec = S * 256 + wq * 64 + l;
-    uint4 a = make_uint4(0, 0, 0, 0), b = a;
-    if (rec < nrec) {
-        a = db[rec * 2 * ncols + 2 * c];
-        b = db[rec * 2 * ncols + 2 * c + 1];
+    const uint32_t nw = ntiles - 8 * c < 8 ? ntiles - 8 * c : 8;       // uniform
+    uint32_t wd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ntiles % 8 == 0) {
+        uint4 a = make_uint4(0, 0, 0, 0), b = a;
+        if (rec < nrec) {
+            a = db[rec * 2 * ncols + 2 * c];
+            b = db[rec * 2 * ncols + 2 * c + 1];
+        }
+        wd[0] = a.x, wd[1] = a.y, wd[2] = a.z, wd[3] = a.w, wd[4] = b.x, wd[5] = b.y, wd[6] = b.z, wd[7] = b.w;
+    } else if (rec < nrec) {
+        const uint32_t* row = reinterpret_cast<const uint32_t*>(db) + rec * ntiles + 8 * c;
+#pragma unroll
+        for (int wi = 0; wi < 8; ++wi)
+            if ((uint32_t)wi < nw) wd[wi] = row[wi];
     }
-    const uint32_t wd[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     const uint32_t g = 2 * wq + (l >> 5);
 #pragma unroll
     for (int wi = 0; wi < 8; ++wi) {
+        if ((uint32_t)wi >= nw) break;                                  // the column's tiles end here
         uint32_t out = 0;
 #pragma unroll
         for (int bb = 0; bb < 32; ++bb) {
@@ -236,7 +269,7 @@ __global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, 
             out = l == (uint32_t)bb ? (uint32_t)m : out;
             out = l == (uint32_t)bb + 32 ? (uint32_t)(m >> 32) : out;
         }
-        dbs[((S * ncols + c) * 256 + 32 * wi + (l & 31)) * 8 + g] = out;
+        dbs[((S * ntiles + 8 * c + wi) * 32 + (l & 31)) * 8 + g] = out;
     }
 }
 
@@ -249,13 +282,15 @@ __global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, 
 // popcount(acc).  parts[x][8 y words].  One key only (97 us at configs[4]
 // against the MFMA fold's 103): with 4 or 16 keys the per-key scalar loads
 // serialise (131 / 388 us against 104 / 107, profiles/r04/fold_ab/).
+// Any width: a super-group is nrows = 8 * rec_bytes rows, and thread n of
+// column c has a row only if 256 c + n < nrows; the others fold nothing.
 // (Nontemporal DB loads, as the matrix-core fold takes them above 256 MiB,
 // measured 95.2-95.8 against 93.9-94.4 us here at 2^24 records: not used.)
 __global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __restrict__ bits,
                                                             const uint4* __restrict__ dbs, uint64_t nsg,
                                                             uint64_t sg_per_block, uint32_t* __restrict__ parts,
                                                             uint32_t* __restrict__ zero, uint64_t zero_words,
-                                                            uint64_t wlim, uint32_t ncols, uint32_t c0) {
+                                                            uint64_t wlim, uint32_t nrows, uint32_t c0) {
     zero_answers(blockIdx.y == 0 ? zero : nullptr, zero_words);
     const uint32_t n = threadIdx.x, l = n & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -274,15 +309,18 @@ __global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __re
                 if (8 * S + g < wlim) acc = xam(acc, x[g], bits[8 * S + g]);
         }
     };
-    auto at = [&](uint64_t S) { return &dbs[((S * ncols + col) * 256 + n) * 2]; };
-    uint64_t S = s0;
-    for (; S + 1 < s1; S += 2) {
-        const uint4 a0 = at(S)[0], b0 = at(S)[1];
-        const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
-        fold(S, a0, b0);
-        fold(S + 1, a1, b1);
+    const uint64_t row = col * 256 + n;
+    auto at = [&](uint64_t S) { return &dbs[(S * nrows + row) * 2]; };
+    if (row < nrows) {
+        uint64_t S = s0;
+        for (; S + 1 < s1; S += 2) {
+            const uint4 a0 = at(S)[0], b0 = at(S)[1];
+            const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
+            fold(S, a0, b0);
+            fold(S + 1, a1, b1);
+        }
+        if (S < s1) fold(S, at(S)[0], at(S)[1]);
     }
-    if (S < s1) fold(S, at(S)[0], at(S)[1]);
     const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc) & 1) != 0);
     if (l < 2)
         parts[(uint64_t)blockIdx.x * (8u * gridDim.y) + 8 * blockIdx.y + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
@@ -291,12 +329,12 @@ __global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __re
 uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * 256 * rec_bytes; }
 
 hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st) {
-    if (!dpfh::rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
-    const uint64_t nsg = (nrec + 255) / 256, C = rec_bytes / 32;
+    if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
+    const uint64_t nsg = (nrec + 255) / 256, C = dpfh::rec_cols(rec_bytes);
     return dpfh::for_each_span(nsg, dpfh::slice_db_span(C), [&](uint64_t S0, uint64_t n) {
         hipLaunchKernelGGL(k_slice_db, dim3((uint32_t)(n * C)), dim3(256), 0, st,
                            reinterpret_cast<const uint4*>(db + S0 * 256 * rec_bytes), nrec - S0 * 256, (uint32_t)C,
-                           reinterpret_cast<uint32_t*>(dbs + S0 * 256 * rec_bytes));
+                           dpfh::rec_tiles(rec_bytes), reinterpret_cast<uint32_t*>(dbs + S0 * 256 * rec_bytes));
         return hipGetLastError();
     });
 }
@@ -310,7 +348,8 @@ struct SlicedFold {
     uint64_t wpk;
     const uint8_t* dbs;
     uint64_t nsg;
-    uint32_t C;
+    uint32_t C;                    // columns: rec_cols(rec_bytes)
+    uint64_t rec_bytes;
     uint32_t* parts;
     dpfh::FoldLimits lim;
     uint64_t cus;
@@ -328,28 +367,35 @@ hipError_t launch_mfma(const SlicedFold& f, const uint32_t* bits, uint32_t nk, u
     static_assert(32 * MT * CG * 32 <= (int)dpfh::kFoldPartBytes, "a workgroup's partial fits its 16 KiB");
     static int occ = [] {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma<MT, NT, SG, CG, false, WPE>, 64 * NW, 0) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fold_mfma<MT, NT, SG, CG, false, WPE, false>, 64 * NW, 0) !=
                 hipSuccess || n < 1)
             n = 1;
         return n;
     }();
     const dpfh::FoldKnobs& knobs = fold_knobs();
-    const bool ntdb = dpfh::fold_ntdb(f.nsg, f.C, knobs.nt_min);
+    const bool ntdb = dpfh::fold_ntdb_any(f.nsg, f.rec_bytes, knobs.nt_min);
     const uint64_t resident =
-        f.cus * dpfh::fold_per_cu(f.C, MT, ntdb, dpfh::fold_db_bytes(f.nsg, f.C), occ, knobs.per_cu);
-    return dpfh::plan_fold_mfma(f.nsg, f.C, T, f.lim, resident, clear_words).for_each_launch([&](const dpfh::FoldLaunch& l) {
+        f.cus * dpfh::fold_per_cu(f.C, MT, ntdb, dpfh::fold_db_bytes_any(f.nsg, f.rec_bytes), occ, knobs.per_cu);
+    const uint32_t ntiles = dpfh::rec_tiles(f.rec_bytes);
+    return dpfh::plan_fold_mfma(f.nsg, f.C, T, f.lim, resident, clear_words, f.rec_bytes)
+        .for_each_launch([&](const dpfh::FoldLaunch& l) {
         const uint32_t* b = bits + l.sel_off;
         const uint4* d = reinterpret_cast<const uint4*>(f.dbs + l.db_off);
         uint32_t* z = l.clear_words ? ans : nullptr;
         const dim3 grid((uint32_t)l.blocks, (uint32_t)l.gy);
-        if (ntdb)
-            hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, CG, true, WPE>), grid, dim3(64 * NW), 0, f.st, b, f.wpk, d, l.n,
-                               nk, l.spb, f.parts, z, l.clear_words, l.wlim(f.wpk), f.C, (uint32_t)l.g0);
-        else
-            hipLaunchKernelGGL((k_fold_mfma<MT, NT, SG, CG, false, WPE>), grid, dim3(64 * NW), 0, f.st, b, f.wpk, d, l.n,
-                               nk, l.spb, f.parts, z, l.clear_words, l.wlim(f.wpk), f.C, (uint32_t)l.g0);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(64 * NW), 0, f.st, b, f.wpk, d, l.n, nk, l.spb, f.parts, z,
+                               l.clear_words, l.wlim(f.wpk), ntiles, (uint32_t)l.g0);
+        };
+        if (ntiles % 8 == 0) {
+            if (ntdb) launch(k_fold_mfma<MT, NT, SG, CG, true, WPE, true>);
+            else launch(k_fold_mfma<MT, NT, SG, CG, false, WPE, true>);
+        } else {
+            if (ntdb) launch(k_fold_mfma<MT, NT, SG, CG, true, WPE, false>);
+            else launch(k_fold_mfma<MT, NT, SG, CG, false, WPE, false>);
+        }
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        return launch_xor_parts(f.parts, l.blocks, nk, 32u * MT, (uint32_t)(8 * CG * l.gy), ans, 8ull * f.C,
+        return launch_xor_parts(f.parts, l.blocks, nk, 32u * MT, (uint32_t)(8 * CG * l.gy), ans, ntiles,
                                 (uint32_t)(8 * CG * l.g0), f.st);
     });
 }
@@ -357,13 +403,14 @@ hipError_t launch_mfma(const SlicedFold& f, const uint32_t* bits, uint32_t nk, u
 // One key over the sliced DB (k_fold_sliced_direct).  parts[x][8 y words] of a
 // launch: x * y * 32 bytes, far inside the partials area.
 hipError_t launch_sliced_direct(const SlicedFold& f, uint32_t* ans) {
-    return dpfh::plan_fold_sliced_direct(f.nsg, f.C, f.lim, f.cus).for_each_launch([&](const dpfh::FoldLaunch& l) {
+    const dpfh::SlicedFoldPlan p = dpfh::plan_fold_sliced_direct(f.nsg, f.C, f.lim, f.cus, f.rec_bytes);
+    return p.for_each_launch([&](const dpfh::FoldLaunch& l) {
         hipLaunchKernelGGL(k_fold_sliced_direct, dim3((uint32_t)l.blocks, (uint32_t)l.gy), dim3(256), 0, f.st, f.bits,
                            reinterpret_cast<const uint4*>(f.dbs), f.nsg, l.spb, f.parts, l.clear_words ? ans : nullptr,
-                           l.clear_words, f.wpk, f.C, (uint32_t)l.g0);
+                           l.clear_words, f.wpk, (uint32_t)(8 * f.rec_bytes), (uint32_t)l.g0);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        return launch_xor_parts(f.parts, l.blocks, 1u, 1u, (uint32_t)(8 * l.gy), ans, 8ull * f.C, (uint32_t)(8 * l.g0),
-                                f.st);
+        return launch_xor_parts(f.parts, l.blocks, 1u, 1u, (uint32_t)(8 * l.gy), ans, dpfh::rec_tiles(f.rec_bytes),
+                                (uint32_t)(8 * l.g0), f.st);
     });
 }
 
@@ -371,19 +418,20 @@ hipError_t launch_sliced_direct(const SlicedFold& f, uint32_t* ans) {
 
 hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
                                   uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st) {
-    if (!dpfh::rec_bytes_ok(rec_bytes)) return hipErrorInvalidValue;
+    if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
     if (nkeys == 0) return hipSuccess;
     if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, st);
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
-    const uint32_t C = (uint32_t)(rec_bytes / 32);
-    const SlicedFold f{bits, words_per_key, dbs, (nrec + 255) / 256, C, parts, fold_limits(), (uint64_t)cu_count(), st};
+    const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
+    const SlicedFold f{bits,  words_per_key, dbs,          (nrec + 255) / 256,   C, rec_bytes,
+                       parts, fold_limits(), (uint64_t)cu_count(), st};
     if (nkeys == 1) return launch_sliced_direct(f, ans);   // popcount fold, no MFMA
     const int cg = dpfh::fold_cg(C, fold_knobs().wide_cg);
     for (uint32_t k0 = 0; k0 < nkeys; k0 += dpfh::kFoldKeyGroup) {
         const uint32_t nk = nkeys - k0 < dpfh::kFoldKeyGroup ? nkeys - k0 : dpfh::kFoldKeyGroup;
         const uint32_t* b = bits + (uint64_t)k0 * words_per_key;
-        const uint64_t zw = dpfh::fold_clear_words(nkeys, C, k0);
-        uint32_t* a = ans + (uint64_t)k0 * 8 * C;
+        const uint64_t zw = dpfh::fold_clear_words_any(nkeys, rec_bytes, k0);
+        uint32_t* a = ans + (uint64_t)k0 * T;
         hipError_t e;
         static_assert(dpfh::kFoldTileCount == 7, "one case per tile shape");
         switch (dpfh::fold_tile_index(nk, cg)) {

@@ -18,13 +18,15 @@ namespace dpfk {
 
 // ans[k * ans_words + off + i] ^= XOR over workgroups p of parts[p][k][i]
 // (k < nkeys, i < pwords; pkeys keys per part).  Block (x, y): 256 words x
-// parts y, y + gridDim.y, ...; one atomicXor each.
+// parts y, y + gridDim.y, ...; one atomicXor each.  Part words at or past
+// ans_words (the absent bit tiles of a record of any width) are not read.
 __global__ __launch_bounds__(256) void k_xor_parts(const uint32_t* __restrict__ parts, uint64_t nparts, uint32_t nkeys,
                                                    uint32_t pkeys, uint32_t pwords, uint32_t* __restrict__ ans,
                                                    uint64_t ans_words, uint32_t off) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nkeys * pwords) return;
     const uint32_t k = t / pwords, i = t % pwords;
+    if ((uint64_t)off + i >= ans_words) return;
     uint32_t v = 0;
     // Eight independent loads in flight per step (a strided loop of single
     // loads left the kernel at ~5 us, mostly dependent L2 round trips).

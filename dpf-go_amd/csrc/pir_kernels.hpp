@@ -37,6 +37,16 @@ hipError_t launch_pir_fold(const uint32_t* bits, uint64_t words_per_key, const u
 // records [256 S0, ...) into dbs + S0 * 256 * rec_bytes writes what slicing
 // the whole DB writes there.  Same bits / parts / ans contract as
 // launch_pir_fold; ans is [nkeys][rec_bytes].
+// The sliced launchers here and below take every rec_bytes that is a positive
+// multiple of 4 (dpfh::rec_bytes_any_ok): as rows, dbs[S][p][g] with
+// p < 8 * rec_bytes the record's bit position, a super-group 8 * rec_bytes
+// rows with no padding behind it; a record is rec_bytes / 4 bit tiles of 32
+// rows in ceil(rec_bytes / 32) columns, the last one possibly short
+// (pir_fold_plan.hpp).  For multiples of 32 that is the layout above, and
+// the kernels run their whole-column instantiations.  Row-major records,
+// messages and answers are [n][rec_bytes], tightly packed: only their base
+// pointers are 16-byte aligned.  The C ABI's _wide entry points keep the
+// multiple-of-32 rule in front of these launchers; the _any ones do not.
 using dpfh::kFoldMaxRecBytes;   // 32768
 uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes);
 hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, uint8_t* dbs, hipStream_t st);

@@ -114,6 +114,15 @@ SIGNATURES = {
     "dpf_pir_db_write": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_pir_db_create_wide": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_rec_bytes": (_sz, [_vp]),
+    "dpf_pir_db_sliced_size_any": (_sz, [_u64, _sz]),
+    "dpf_pir_db_slice_any_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_xor_fold_sliced_any_dev": (_int, [_int, _vp, _sz, _sz, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_answer_sliced_any_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_db_update_sliced_any_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp, _sz, _vp]),
+    "dpf_pir_db_gather_sliced_any_dev": (_int, [_int, _vp, _u64, _sz, _vp, _sz, _vp, _vp]),
+    "dpf_xor_scatter_sliced_any_dev": (_int, [_int, _vp, _sz, _sz, _vp, _vp, _u64, _sz, _vp]),
+    "dpf_pir_write_sliced_any_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_create_any": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_nrec": (_u64, [_vp]),
     "dpf_pir_db_update": (_int, [_vp, _u64p, _u8p, _sz]),
     "dpf_pir_db_read": (_int, [_vp, _u64p, _sz, _u8p]),
@@ -627,6 +636,61 @@ def pir_write_sliced_wide_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_ms
                                                _stream_handle(stream)))
 
 
+# ---- records of any width (a multiple of 4 bytes) over the sliced layout ----
+def pir_db_sliced_size_any(nrec: int, rec_bytes: int) -> int:
+    """Bytes of the bit-sliced layout of nrec records of rec_bytes (a multiple of 4; 0 for a bad width)."""
+    return int(lib().dpf_pir_db_sliced_size_any(nrec, rec_bytes))
+
+
+def pir_db_slice_any_dev(d_db, nrec: int, rec_bytes: int, d_dbs, device: int = 0, stream=None) -> None:
+    """Bit-sliced copy dbs[S][p][g] of a row-major DB of rec_bytes-byte records (any multiple of 4)."""
+    _check(lib().dpf_pir_db_slice_any_dev(device, _ptr(d_db), nrec, rec_bytes, _ptr(d_dbs), _stream_handle(stream)))
+
+
+def xor_fold_sliced_any_dev(d_bits, bits_stride: int, nkeys: int, d_dbs, nrec: int, rec_bytes: int, d_ans, d_work,
+                            device: int = 0, stream=None) -> None:
+    """xor_fold_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_xor_fold_sliced_any_dev(device, _ptr(d_bits), bits_stride, nkeys, _ptr(d_dbs), nrec, rec_bytes,
+                                             _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_answer_sliced_any_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_dbs, nrec: int, rec_bytes: int, d_ans,
+                              d_work, prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """pir_answer_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_pir_answer_sliced_any_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix,
+                                               _ptr(d_dbs), nrec, rec_bytes, _ptr(d_ans), _ptr(d_work),
+                                               _stream_handle(stream)))
+
+
+def pir_db_update_sliced_any_dev(d_dbs, nrec: int, rec_bytes: int, d_idx, d_recs, n: int, device: int = 0,
+                                 stream=None) -> None:
+    """pir_db_update_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_pir_db_update_sliced_any_dev(device, _ptr(d_dbs), nrec, rec_bytes, _ptr(d_idx), _ptr(d_recs), n,
+                                                  _stream_handle(stream)))
+
+
+def pir_db_gather_sliced_any_dev(d_dbs, nrec: int, rec_bytes: int, d_idx, n: int, d_out, device: int = 0,
+                                 stream=None) -> None:
+    """pir_db_gather_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_pir_db_gather_sliced_any_dev(device, _ptr(d_dbs), nrec, rec_bytes, _ptr(d_idx), n, _ptr(d_out),
+                                                  _stream_handle(stream)))
+
+
+def xor_scatter_sliced_any_dev(d_bits, bits_stride: int, nkeys: int, d_msgs, d_dbs, nrec: int, rec_bytes: int,
+                               device: int = 0, stream=None) -> None:
+    """xor_scatter_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_xor_scatter_sliced_any_dev(device, _ptr(d_bits), bits_stride, nkeys, _ptr(d_msgs), _ptr(d_dbs),
+                                                nrec, rec_bytes, _stream_handle(stream)))
+
+
+def pir_write_sliced_any_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_msgs, d_dbs, nrec: int, rec_bytes: int,
+                             d_work, prefix_bits: int = 0, prefix: int = 0, device: int = 0, stream=None) -> None:
+    """pir_write_sliced_wide_dev for any rec_bytes that is a multiple of 4."""
+    _check(lib().dpf_pir_write_sliced_any_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, prefix,
+                                              _ptr(d_msgs), _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work),
+                                              _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -636,8 +700,9 @@ def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
 
 
 class PirDB:
-    """A DB of rec_bytes-byte records (a multiple of 32; default 32 whatever
-    the array's shape) resident in HBM, sharded by top-level subtree over
+    """A DB of rec_bytes-byte records (any width from 1 byte; default 32
+    whatever the array's shape; widths that are not a multiple of 32 go
+    through dpf_pir_db_create_any) resident in HBM, sharded by top-level subtree over
     ngpus GPUs; answer() returns each key's XOR-inner-product, (n, rec_bytes)
     (host XOR of the per-GPU partials)."""
 
@@ -651,8 +716,10 @@ class PirDB:
         h = _vp()
         if rec_bytes == 32:
             _check(lib().dpf_pir_db_create(_buf(d), nrec, logN, ngpus, ctypes.byref(h)))
-        else:
+        elif rec_bytes % 32 == 0:
             _check(lib().dpf_pir_db_create_wide(_buf(d), nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
+        else:
+            _check(lib().dpf_pir_db_create_any(_buf(d), nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
         self._h = h
 
     @property

@@ -376,6 +376,55 @@ int dpf_pir_write_wide_dev(int device, const uint8_t* d_keys, size_t key_len, si
 int dpf_pir_write_sliced_wide_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
                                   uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_dbs,
                                   uint64_t nrec, size_t rec_bytes, void* d_work, void* stream);
+/* Records of any width over the sliced layout.  The layout is defined for
+ * every rec_bytes that is a positive multiple of 4 up to
+ * DPF_PIR_MAX_REC_BYTES, and is ABI.  As a u32 array:
+ *   dbs[S][p][g]: super-group S of 256 records, p < 8*rec_bytes the bit
+ *   position of the record (bit p%8 of its byte p/8), record group g < 8;
+ *   bit j of the word = bit p of record 256*S + 32*g + j.  Records past nrec
+ *   read as 0.
+ * A super-group is 8*rec_bytes rows of 8 words and the next one follows
+ * directly: rows past a record's last bit do not exist.  The size is
+ * ceil(nrec/256) * 256 * rec_bytes bytes (minimum 16), a chunk that starts at
+ * a multiple of 256 records is still a contiguous sub-range (at byte
+ * S0*256*rec_bytes), and for rec_bytes = 32*C the layout is the wide layout
+ * above, byte for byte (p = 256*c + n).  Stored this way a table of 16-byte
+ * records takes half the memory, and the fold half the DB traffic, of the
+ * same table padded to 32 bytes.
+ * A multiple of 4 because a tile of 32 rows is the unit of the fold, of an
+ * answer word and of a selection word; other widths go through
+ * dpf_pir_db_create_any below, which pads records to the next multiple of 4 on
+ * the device.  The record is rec_bytes/4 such tiles in ceil(rec_bytes/32)
+ * columns of up to 8, the last column possibly short; the kernels are those of
+ * the _wide entry points, which skip the tiles a record does not have (no
+ * load, no answer word).
+ * Each _any entry point below is its _wide counterpart with that width rule:
+ * rec_bytes that is 0, not a multiple of 4 or above DPF_PIR_MAX_REC_BYTES is
+ * DPF_ERR_PARAM (the size function returns 0), checked before any device call
+ * and before the other arguments; alignment (of the base pointers: rows of
+ * d_db, d_recs, d_out, d_msgs and d_ans are [n][rec_bytes], tightly packed,
+ * and need not be 16-byte aligned themselves), null, nrec, bits_stride and
+ * prefix rules, workspace sizes and asynchrony are those of the _wide form.
+ * The _wide entry points keep rejecting widths that are not multiples of 32. */
+size_t dpf_pir_db_sliced_size_any(uint64_t nrec, size_t rec_bytes);
+int dpf_pir_db_slice_any_dev(int device, const uint8_t* d_db, uint64_t nrec, size_t rec_bytes, uint8_t* d_dbs,
+                             void* stream);
+int dpf_xor_fold_sliced_any_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                void* stream);
+int dpf_pir_answer_sliced_any_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                                  uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_dbs, uint64_t nrec,
+                                  size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream);
+int dpf_pir_db_update_sliced_any_dev(int device, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                     const uint64_t* d_idx, const uint8_t* d_recs, size_t n, void* stream);
+int dpf_pir_db_gather_sliced_any_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                     const uint64_t* d_idx, size_t n, uint8_t* d_out, void* stream);
+int dpf_xor_scatter_sliced_any_dev(int device, const uint8_t* d_bits, size_t bits_stride, size_t nkeys,
+                                   const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                   void* stream);
+int dpf_pir_write_sliced_any_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                                 uint32_t prefix_bits, uint64_t prefix, const uint8_t* d_msgs, uint8_t* d_dbs,
+                                 uint64_t nrec, size_t rec_bytes, void* d_work, void* stream);
 /* Tuning / test limits of the XOR fold launches (process-wide; 0 = default):
  * at most max_blocks workgroups per fold launch (default and maximum 1024),
  * and at most max_sg_per_block super-groups of 256 records per matrix-core
@@ -422,6 +471,18 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t key_len, size_t nke
  * bytes. */
 int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
                            void** handle);
+/* The same for records of every width, 1 .. DPF_PIR_MAX_REC_BYTES bytes (else
+ * DPF_ERR_PARAM with *handle = NULL).  db is [nrec][rec_bytes], tightly
+ * packed.  The shards hold each record in (rec_bytes+3)&~3 bytes of the
+ * any-width sliced layout above; the pad bytes are zero and stay zero.
+ * Upload, answers, updates, reads and writes convert between the caller's
+ * tight rows and the device's padded ones by pitched copies, so
+ * dpf_pir_answer, dpf_pir_db_update, dpf_pir_db_read and dpf_pir_db_write take
+ * and return rows of dpf_pir_db_rec_bytes(handle) bytes, the caller's width,
+ * under their contracts below.  With env DPF_PIR_FOLD=lds (row-major shards) a
+ * width that is not a multiple of 32 is DPF_ERR_PARAM with *handle = NULL.
+ * For a multiple of 32 the handle is what dpf_pir_db_create_wide makes. */
+int dpf_pir_db_create_any(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle);
 size_t dpf_pir_db_rec_bytes(void* handle);
 /* Records the handle was created with (0 for NULL). */
 uint64_t dpf_pir_db_nrec(void* handle);
