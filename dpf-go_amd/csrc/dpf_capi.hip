@@ -768,6 +768,75 @@ int dpf_eval_batch_dev(int device, const uint8_t* d_keys, size_t klen, size_t nk
     return DPF_OK;
 }
 
+// Introspection: the launchers' own plans (tree_plan.hpp) as plain C structs.
+static dpf_tree_form c_form(const dpfh::TreeForm& t) {
+    dpf_tree_form f;
+    memset(&f, 0, sizeof f);
+    f.d = t.d;
+    f.block = t.block;
+    f.w = t.W;
+    f.ltop = t.ltop;
+    f.units_log = t.units_log;
+    f.walk = (uint32_t)t.walk;
+    f.l1 = t.l1;
+    f.uniform = t.uniform;
+    f.nodes = t.nodes;
+    f.raw = t.raw;
+    f.cw_lds = t.cw_lds;
+    f.feedback = t.feedback;
+    f.prio_small = t.prio_small;
+    f.nunits = t.nunits;
+    f.grid = t.grid;
+    f.sub_base = t.sub_base;
+    return f;
+}
+static uint64_t form_cus(int cus) { return (uint64_t)(cus > 0 ? cus : dpfk::cu_count()); }
+
+int dpf_tree_form_for(size_t nkeys, uint32_t logN, uint32_t prefix_bits, uint32_t node_level, int cus,
+                      dpf_tree_form* form) {
+    if (form == nullptr || logN > 63) return fail(DPF_ERR_PARAM, "dpf: form query out of range");
+    const uint32_t stop = stop_of(logN);
+    const bool nodes = node_level != 0;
+    const uint32_t depth = nodes ? node_level : stop;
+    if (depth > stop || prefix_bits > depth) return fail(DPF_ERR_PARAM, "dpf: form query out of range");
+    const dpfh::TreeKnobs& k = dpfk::tree_knobs();
+    const uint64_t c = form_cus(cus);
+    const bool raw = !nodes && dpfh::evalfull_raw_ok(nkeys, stop, prefix_bits, c, k);
+    dpfh::TreeForm t;
+    if (!dpfh::tree_form(nkeys, depth, prefix_bits, 0, nodes, raw, c, k.forced_depth, &t))
+        return fail(DPF_ERR_PARAM, "dpf: tree launch refused: more than 2^31 - 1 workgroups");
+    *form = c_form(t);
+    return DPF_OK;
+}
+
+int dpf_eval_form_for(size_t nkeys, size_t ppk, uint32_t logN, size_t work_bytes, int xs_aligned16, int cus,
+                      dpf_eval_form* form) {
+    if (form == nullptr || logN > 4096 || nkeys == 0 || ppk == 0)
+        return fail(DPF_ERR_PARAM, "dpf: form query out of range");
+    const uint32_t stop = stop_of(logN);
+    const size_t ekb = pir_ek_bytes(nkeys, logN);
+    if (work_bytes < nkeys * dpfk::ek_words(stop) * 4) return fail(DPF_ERR_PARAM, "dpf: Eval workspace too small");
+    dpfh::EvalForm e;
+    if (!dpfh::eval_form((uint64_t)nkeys * ppk, ppk, stop, logN, work_bytes > ekb ? work_bytes - ekb : 0,
+                         xs_aligned16 != 0, form_cus(cus), dpfk::tree_knobs(), &e))
+        return fail(DPF_ERR_PARAM, "dpf: Eval launch refused: more than 2^31 - 1 workgroups");
+    memset(form, 0, sizeof *form);
+    form->level = e.L;
+    form->kernel = (uint32_t)e.kernel;
+    form->block = e.block;
+    form->grid = e.grid;
+    form->cw_staged = e.cw_staged;
+    form->ragged = e.ragged;
+    if (e.L > 0) form->nodes = c_form(e.nodes);
+    if (e.L > 0 && dpfk::get_eval_trie() && dpfk::eval_trie_ok(stop, logN, ppk, e.L)) {
+        form->kernel = DPF_EVAL_TRIE_KERNEL;   // launch_eval: the trie kernel takes the queries
+        form->block = 0;
+        form->grid = 0;
+        form->cw_staged = form->ragged = 0;
+    }
+    return DPF_OK;
+}
+
 int dpf_expand_keys_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, void* d_work,
                         void* stream) {
     if (int rc = check_key(klen, logN)) return rc;

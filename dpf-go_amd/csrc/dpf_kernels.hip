@@ -66,7 +66,7 @@ __device__ __forceinline__ void prio_step(Ctx& c) {
         prio_by_lead(c.prog, c.pslot, ++c.groups, 1, kPrioFar);
         return;
     }
-    constexpr bool small = DMAX <= 5;
+    constexpr bool small = DMAX <= (int)dpfh::kPrioSmallMaxD;   // dpfh::TreeForm::prio_small
     constexpr uint32_t total = DMAX >= 2 ? 1u << (DMAX - 2) : 1u;   // 4-leaf groups per thread
     const uint32_t d = ++c.groups;
     constexpr uint32_t den = small ? 8 : 16;
@@ -268,7 +268,9 @@ __global__ void k_unpack(const uint8_t* __restrict__ keys, uint64_t key_len, uin
 // NODES: the same walk, but the 2^D nodes at level ltop + D are written to
 // (uint4*)out / out_t at [key*out_stride + (u mod 2^units_log) * 2^D].
 // Precondition: blockDim.x = 2^W, a power of two from 64 to kTreeBlockMax
-// (pick_block returns nothing else).
+// (dpfh::pick_block returns nothing else).  Which of its run-time forms a
+// launch takes is written down in dpfh::TreeForm (tree_plan.hpp), whose rules
+// for cw_lds, the walk kind and feedback are the ones this kernel applies.
 template <int D, bool UNIFORM, bool NODES, bool RAW = false>
 __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const uint32_t* __restrict__ ekeys, uint32_t stop,
                                                         uint64_t nunits, uint32_t units_log, uint32_t ltop,
@@ -300,6 +302,7 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
     // that runs while the CU is otherwise idle.  Here lane l of wave 0 loads
     // level l's CW with vector loads issued before the table fill, and the
     // walks read it from LDS (in-order returns: no wait beyond the round's own).
+    // Rule: dpfh::tree_cw_lds (uniform && units_log >= W; stop <= 64 = dpfh::kCwLdsLevels always).
     __shared__ __attribute__((aligned(16))) uint32_t s_cw[8 * 64];
     const bool cw_lds = UNIFORM && stop <= 64 && units_log >= W && (uint64_t)blockIdx.x * B < nunits;   // workgroup-uniform
     const bool cw_mine = cw_lds && threadIdx.x < ltop;
@@ -323,7 +326,8 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
     // Feedback priority only where the workgroup holds all 16 waves of its CU (one
     // kTreeBlockBig-thread workgroup per CU): with two workgroups per CU a
     // wave sees half of its SIMD's waves, and steering by them was 3% slower.
-    if (UNIFORM && !NODES && D >= (int)kFeedbackMinD && B == 1024u) {
+    // Rule: dpfh::tree_feedback.
+    if (UNIFORM && !NODES && D >= (int)kFeedbackMinD && B == (uint32_t)kTreeBlockBig) {
         c.prog = prog_slots(s_prog, c.pslot);
         c.prog[c.pslot] = 0;
     }
@@ -351,7 +355,7 @@ __global__ __launch_bounds__(kTreeBlockMax, kTreeWaves) void k_evalfull(const ui
         // instead of (B/64) ltop (configs[4]: 33 vs 96, configs[3]: 39 vs 144).
         constexpr uint32_t F = 6, kFs = 1u << F;   // paths of the shared walk: 2^F
         __shared__ uint32_t s_front[5 * kFs];   // SoA: word k of node j at k * kFs + j
-        if (W >= 7 && cw_lds) {   // uniform
+        if (W >= 7 && cw_lds) {   // uniform; which walk: dpfh::tree_walk, l1 as dpfh::TreeForm::l1
             const uint32_t l1 = ltop - W + F;
             auto put = [&](uint32_t j, const Node& m) {
                 s_front[j] = m.s.c0; s_front[kFs + j] = m.s.c1; s_front[2 * kFs + j] = m.s.c2;
@@ -563,7 +567,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
 // reads (a different LDS object) never wait on them.
 // UNI only: a wave's 64 pairs are 128 consecutive queries of one key, and nq
 // is even (pts_per_key % 128 == 0), so a pair's points are one 16-byte load.
-constexpr int kEvalPBlock = 1024;
+// (kEvalPBlock threads: tree_plan.hpp, with the grid that launch_eval gives it.)
 constexpr uint32_t kEvalPrioFar = 3;   // prio_by_lead every 4 pairs: a lead of 4 is near, up to 4 * kEvalPrioFar far
 struct EvalSlots {
     uint4 x[2][64];      // x(i), x(i+1): {x0, x1} as two uint64
@@ -624,7 +628,7 @@ __global__ __launch_bounds__(kEvalPBlock, 1) void k_eval_persist(const uint32_t*
     };
     const uint64_t rec = (uint64_t)(stop + 2) * 8;
     const uint32_t ncw = (stop - L) * 8 + 4;
-    const bool cw_slots = ncw <= 64;      // uniform
+    const bool cw_slots = ncw <= 64;      // uniform; rule: dpfh::eval_cw_staged
     auto issue_x = [&](uint64_t i, int slot) __attribute__((always_inline)) {
         glds(xs + 2 * pair_of(i), &sl.x[slot][0], 16);
     };
@@ -765,93 +769,28 @@ int cu_count() {
     return cus;
 }
 
-// Workgroup size for a grid of n threads: full maxb-thread groups (maxb a
-// power of two) once the grid covers every CU, otherwise the smallest power
-// of two (>= one wave) that spreads it over all CUs, so that a small batch is
-// not packed onto a few CUs whose LDS pipe then serialises it.
-static uint32_t pick_block(uint64_t n, uint32_t maxb) {
-    const uint64_t cus = (uint64_t)cu_count();
-    uint32_t b = 64;
-    while (b < maxb && n > cus * b) b <<= 1;
-    return b;
-}
-
-// Per-thread subtree depth D and workgroup size.  A thread walks span - D
-// levels (one AES each) and expands 3 * 2^D - 2 AES depth-first: deeper
-// subtrees amortise the walk, shallower ones give more, shorter threads.
-// Time model fitted to tools/archive/exp_latency.sh on MI355X (all batch shapes
-// within ~8%): a thread's AES take max(kLat, w * kPerWave) each, w = waves
-// per CU (<= 16; more threads run in further rounds).  The throughput regime
-// (4096 keys x logN=20) takes D = 7; one key at logN=20 takes D = 0, 14 AES
-// deep per thread instead of 197 at D = 7.
-// DPF_SUBTREE_DEPTH overrides the choice (measurement only).
-struct TreeShape {
-    uint32_t d, block;
-};
-static TreeShape pick_shape(uint32_t span, uint64_t nkeys, bool nodes, uint32_t prefix_bits) {
-    static const int forced = [] {
-        const char* e = getenv("DPF_SUBTREE_DEPTH");
-        return e ? atoi(e) : -1;
+// The measurement switches of the launch plans (tree_plan.hpp), read from the
+// environment once per process.
+const dpfh::TreeKnobs& tree_knobs() {
+    static const dpfh::TreeKnobs knobs = [] {
+        dpfh::TreeKnobs k;
+        if (const char* e = getenv("DPF_SUBTREE_DEPTH")) k.forced_depth = atoi(e);
+        if (const char* e = getenv("DPF_RAW_KEYS")) k.raw_keys = e[0] != '0';
+        if (const char* e = getenv("DPF_EVAL_PERSIST"); e && *e) k.eval_persist = atoi(e);
+        if (const char* e = getenv("DPF_EVAL_UNIFORM")) k.eval_uniform = e[0] != '0';
+        if (const char* e = getenv("DPF_EVAL_LEVEL_SHIFT"); e && *e) k.eval_level_shift = atoi(e);
+        if (const char* e = getenv("DPF_EVAL_MODE")) k.eval_plain = e[0] == 'p';
+        return k;
     }();
-    const uint32_t dmax = span < kMaxD ? span : kMaxD;
-    auto threads = [&](uint32_t dd) { return span - dd >= 40 ? ~0ull : nkeys << (span - dd); };
-    auto block = [&](uint32_t dd) {
-        return pick_block(threads(dd), !nodes && dd >= kBigMinD ? (uint32_t)kTreeBlockBig : (uint32_t)kTreeBlock);
-    };
-    if (forced >= 0) {
-        const uint32_t d = dmax < (uint32_t)forced ? dmax : (uint32_t)forced;
-        return {d, block(d)};
-    }
-    constexpr double kLat = 1.9e-6;       // one AES-MMO of a thread on a lightly loaded CU
-    constexpr double kPerWave = 0.2e-6;   // ... per resident wave when the CU's LDS pipe is shared
-    const double wave_slots = 64.0 * cu_count();
-    uint32_t best = dmax;
-    double best_t = 1e30;
-    for (int dd = (int)dmax; dd >= 0; --dd) {
-        const uint32_t d = (uint32_t)dd;
-        double walk = (double)(span - d), lat = 0.0;
-        const double w = (double)threads(d) / wave_slots;                 // waves per CU
-        const double rounds = w > 16.0 ? std::ceil(w / 16.0) : 1.0;
-        const double per = w > 16.0 ? 16.0 * kPerWave : std::max(kLat, w * kPerWave);
-        // The shared workgroup walk (k_evalfull): one wave walks the top
-        // ltop - W + 6 levels alone (latency, once per round of workgroups),
-        // every thread the last W - 6.
-        const uint32_t W = 31u - (uint32_t)__builtin_clz(block(d));
-        if (W >= 7 && span - d >= W) {
-            walk = (double)(W - 6);
-            lat = (double)(span + prefix_bits - d - W + 6) * kLat;
-        }
-        const double work = walk + (nodes ? 2.0 : 3.0) * (double)(1u << d) - 2.0;   // NODES: no leaf AES
-        const double t = rounds * (lat + work * std::max(kLat, per));
-        if (t < best_t * 0.98) {          // prefer the deeper subtree on near-ties (less total work)
-            best_t = t;
-            best = d;
-        }
-    }
-    return {best, block(best)};
+    return knobs;
 }
 
-// What a tree launch over the subtrees (prefix_bits, prefix) down to level
-// `depth` of every key derives from pick_shape; shared by the leaf, node and
-// raw-key launches and by evalfull_raw_ok.
-struct TreeLaunch {
-    uint32_t d;           // per-thread subtree depth
-    uint32_t ltop;        // levels walked per thread
-    uint32_t units_log;   // threads per key = 2^units_log
-    uint64_t nunits, sub_base;
-    dim3 grid, block;
-};
-static TreeLaunch tree_launch(uint64_t nkeys, uint32_t depth, uint32_t prefix_bits, uint64_t prefix, bool nodes) {
-    const TreeShape sh = pick_shape(depth - prefix_bits, nkeys, nodes, prefix_bits);
-    TreeLaunch t;
-    t.d = sh.d;
-    t.ltop = depth - sh.d;
-    t.units_log = t.ltop - prefix_bits;
-    t.nunits = nkeys << t.units_log;
-    t.sub_base = prefix << t.units_log;
-    t.grid = dim3((uint32_t)((t.nunits + sh.block - 1) / sh.block));
-    t.block = dim3(sh.block);
-    return t;
+// The plan of a tree launch (dpfh::tree_form: depth, workgroup, grid and the
+// kernel form) for the calling thread's CU budget; false when it is refused.
+static bool tree_launch(uint64_t nkeys, uint32_t depth, uint32_t prefix_bits, uint64_t prefix, bool nodes, bool raw,
+                        dpfh::TreeForm* t) {
+    return dpfh::tree_form(nkeys, depth, prefix_bits, prefix, nodes, raw, (uint64_t)cu_count(),
+                           tree_knobs().forced_depth, t);
 }
 // f(std::integral_constant<int, D>) for the run-time depth d <= kMaxD.
 template <class F>
@@ -874,42 +813,39 @@ template <bool NODES>
 static hipError_t launch_tree(const uint32_t* ek, uint64_t nkeys, uint32_t stop, uint32_t depth,
                               uint32_t prefix_bits, uint64_t prefix, uint8_t* out, uint8_t* out_t,
                               uint64_t out_stride, hipStream_t st) {
-    const TreeLaunch t = tree_launch(nkeys, depth, prefix_bits, prefix, NODES);
+    dpfh::TreeForm t;
+    if (!tree_launch(nkeys, depth, prefix_bits, prefix, NODES, false, &t)) return hipErrorInvalidValue;
     if (t.nunits == 0) return hipSuccess;
+    const dim3 grid((uint32_t)t.grid), block(t.block);
     with_depth(t.d, [&](auto dd) {
         constexpr int D = decltype(dd)::value;
-        if (t.units_log >= 6)
-            hipLaunchKernelGGL((k_evalfull<D, true, NODES>), t.grid, t.block, 0, st, ek, stop, t.nunits, t.units_log,
+        if (t.uniform)
+            hipLaunchKernelGGL((k_evalfull<D, true, NODES>), grid, block, 0, st, ek, stop, t.nunits, t.units_log,
                                t.ltop, t.sub_base, out, out_t, out_stride);
         else
-            hipLaunchKernelGGL((k_evalfull<D, false, NODES>), t.grid, t.block, 0, st, ek, stop, t.nunits, t.units_log,
+            hipLaunchKernelGGL((k_evalfull<D, false, NODES>), grid, block, 0, st, ek, stop, t.nunits, t.units_log,
                                t.ltop, t.sub_base, out, out_t, out_stride);
     });
     return hipGetLastError();
 }
 
-// One-shot EvalFull straight from the key bytes (RAW): only where every wave
-// owns one key (the shape launch_tree would pick has >= 64 threads per key)
-// and DPF_RAW_KEYS is not 0 (measurement switch).  Any key alignment: the
-// kernel reads from the 4-byte-aligned base below `keys`.
+// One-shot EvalFull straight from the key bytes (RAW): where
+// dpfh::evalfull_raw_ok (every wave owns one key, DPF_RAW_KEYS not 0).  Any
+// key alignment: the kernel reads from the 4-byte-aligned base below `keys`.
 bool evalfull_raw_ok(uint64_t nkeys, uint32_t stop, uint32_t prefix_bits) {
-    static const bool on = [] {
-        const char* e = getenv("DPF_RAW_KEYS");
-        return !(e && e[0] == '0');
-    }();
-    if (!on || nkeys == 0 || prefix_bits > stop) return false;
-    return tree_launch(nkeys, stop, prefix_bits, 0, false).units_log >= 6;   // UNIFORM
+    return dpfh::evalfull_raw_ok(nkeys, stop, prefix_bits, (uint64_t)cu_count(), tree_knobs());
 }
 
 hipError_t launch_evalfull_raw(const uint8_t* keys, uint64_t klen, uint64_t nkeys, uint32_t stop, uint32_t prefix_bits,
                                uint64_t prefix, uint8_t* out, uint64_t out_stride, hipStream_t st) {
-    const TreeLaunch t = tree_launch(nkeys, stop, prefix_bits, prefix, false);
-    if (t.units_log < 6) return hipErrorInvalidValue;
+    dpfh::TreeForm t;
+    if (!tree_launch(nkeys, stop, prefix_bits, prefix, false, true, &t) || !t.uniform) return hipErrorInvalidValue;
     // Aligned base below the batch, the batch's offset from it in kboff.
     const uint64_t kboff = (uintptr_t)keys & 3;
     const uint32_t* kw = reinterpret_cast<const uint32_t*>(keys - kboff);
+    const dim3 grid((uint32_t)t.grid), block(t.block);
     with_depth(t.d, [&](auto dd) {
-        hipLaunchKernelGGL((k_evalfull<decltype(dd)::value, true, false, true>), t.grid, t.block, 0, st, kw, stop,
+        hipLaunchKernelGGL((k_evalfull<decltype(dd)::value, true, false, true>), grid, block, 0, st, kw, stop,
                            t.nunits, t.units_log, t.ltop, t.sub_base, out, nullptr, out_stride, klen, kboff);
     });
     return hipGetLastError();
@@ -925,25 +861,13 @@ hipError_t launch_evalfull(const uint32_t* ek, uint64_t nkeys, uint32_t stop, ui
     return launch_tree<false>(ek, nkeys, stop, stop, prefix_bits, prefix, out, nullptr, out_stride, st);
 }
 
+// The frontier's level and size (tree_plan.hpp) under DPF_EVAL_LEVEL_SHIFT.
 uint32_t eval_frontier_level(uint32_t stop, uint64_t pts_per_key) {
-    // Shared frontier at the deepest level L whose nodes a key's points cover
-    // twice over on average: 2^(L+1) <= ppk, i.e. >= 2 points per frontier
-    // node (L = 9 at 1024 points per key), used when L >= 4.
-    uint32_t L = 0;
-    while (L < kMaxFrontierHbm && L < stop && (2ull << (L + 1)) <= pts_per_key) ++L;
-    // DPF_EVAL_LEVEL_SHIFT=n (measurement only): the frontier n levels deeper.
-    static const int shift = [] {
-        const char* e = getenv("DPF_EVAL_LEVEL_SHIFT");
-        return e && *e ? atoi(e) : 0;
-    }();
-    if (L >= 4 && shift > 0 && L + (uint32_t)shift < stop && L + (uint32_t)shift <= kMaxFrontierHbm) L += shift;
-    return L >= 4 ? L : 0;
+    return dpfh::eval_frontier_level(stop, pts_per_key, tree_knobs().eval_level_shift);
 }
 
 uint64_t eval_frontier_bytes(uint64_t nkeys, uint32_t stop, uint64_t pts_per_key) {
-    const uint32_t L = eval_frontier_level(stop, pts_per_key);
-    if (L == 0) return 0;
-    return ((nkeys << L) * 16 + (nkeys << L) + 255) & ~255ull;
+    return dpfh::eval_frontier_bytes(nkeys, stop, pts_per_key, tree_knobs().eval_level_shift);
 }
 
 // Batched Eval kernel (dpf_set_eval_kernel): 0 = frontier + per-query walks,
@@ -961,14 +885,14 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
                        uint64_t pts_per_key, uint8_t* out, void* frontier, uint64_t frontier_bytes,
                        hipStream_t st) {
     if (nq == 0) return hipSuccess;
-    // DPF_EVAL_MODE=plain forces root walks (measurement only).
-    static const bool plain = [] {
-        const char* e = getenv("DPF_EVAL_MODE");
-        return e && e[0] == 'p';
-    }();
+    // The whole choice (frontier level, kernel, grid) is dpfh::eval_form's.
     const uint64_t nkeys = nq / pts_per_key;
-    uint32_t L = eval_frontier_level(stop, pts_per_key);
-    if (logN > 63 || plain || frontier == nullptr || frontier_bytes < eval_frontier_bytes(nkeys, stop, pts_per_key)) L = 0;
+    const bool xs16 = (reinterpret_cast<uintptr_t>(xs) & 15u) == 0;
+    dpfh::EvalForm f;
+    if (!dpfh::eval_form(nq, pts_per_key, stop, logN, frontier == nullptr ? 0 : frontier_bytes, xs16,
+                         (uint64_t)cu_count(), tree_knobs(), &f))
+        return hipErrorInvalidValue;
+    const uint32_t L = f.L;
     const uint4* fseed = nullptr;
     const uint8_t* ft = nullptr;
     if (L > 0) {
@@ -981,38 +905,13 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
     }
     if (L > 0 && trie_on() && nq == nkeys * pts_per_key && eval_trie_ok(stop, logN, pts_per_key, L))
         return launch_eval_trie(ek, stop, logN, xs, nkeys, pts_per_key, fseed, ft, L, out, st);
-    // Persistent form (k_eval_persist): needs the frontier and wave-uniform keys.
-    static const int persist = [] {
-        const char* e = getenv("DPF_EVAL_PERSIST");
-        return e && *e ? atoi(e) : 1;
-    }();
-    // Its LDS-DMA stages a pair's two points with one 16-byte load from xs + 2*pair,
-    // so it needs a 16-byte-aligned xs; an 8-byte-aligned one (a torch slice
-    // xs[1:]) takes k_eval2, whose loads are 8 bytes wide.
-    const bool xs16 = (reinterpret_cast<uintptr_t>(xs) & 15u) == 0;
-    if (persist && xs16 && L > 0 && pts_per_key % 128 == 0 && nq == nkeys * pts_per_key &&
-        nq >= 2 * (uint64_t)kEvalPBlock) {
-        const uint64_t want = (nq / 2 + kEvalPBlock - 1) / kEvalPBlock;
-        const uint64_t cus = (uint64_t)cu_count();
-        hipLaunchKernelGGL(k_eval_persist, dim3((uint32_t)(want < cus ? want : cus)), dim3(kEvalPBlock), 0, st, ek, stop,
-                           logN, xs, nq, pts_per_key, fseed, ft, L, out);
-        return hipGetLastError();
-    }
-    const uint64_t nthreads = (nq + 1) / 2;
-    const uint32_t block = pick_block(nthreads, kBlock);
-    const uint64_t blocks = (nthreads + block - 1) / block;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;   // one pair per thread: no grid-stride loop to fall back on
-    // Wave-uniform keys when every wave's 128 queries share one key.
-    static const bool uni_on = [] {
-        const char* e = getenv("DPF_EVAL_UNIFORM");
-        return !(e && e[0] == '0');
-    }();
-    if (uni_on && pts_per_key % 128 == 0 && block % 64 == 0)
-        hipLaunchKernelGGL(k_eval2<true>, dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop, logN, xs, nq,
-                           pts_per_key, fseed, ft, L, out);
+    const dim3 grid((uint32_t)f.grid), block(f.block);
+    if (f.kernel == dpfh::kEvalPersist)
+        hipLaunchKernelGGL(k_eval_persist, grid, block, 0, st, ek, stop, logN, xs, nq, pts_per_key, fseed, ft, L, out);
+    else if (f.kernel == dpfh::kEvalPairUniform)
+        hipLaunchKernelGGL(k_eval2<true>, grid, block, 0, st, ek, stop, logN, xs, nq, pts_per_key, fseed, ft, L, out);
     else
-        hipLaunchKernelGGL(k_eval2<false>, dim3((uint32_t)blocks), dim3(block), 0, st, ek, stop, logN, xs, nq,
-                           pts_per_key, fseed, ft, L, out);
+        hipLaunchKernelGGL(k_eval2<false>, grid, block, 0, st, ek, stop, logN, xs, nq, pts_per_key, fseed, ft, L, out);
     return hipGetLastError();
 }
 

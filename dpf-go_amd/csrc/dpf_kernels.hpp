@@ -3,28 +3,31 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tree_plan.hpp"
+
 namespace dpfk {
 
-constexpr int kBlock = 512;    // threads per workgroup (8 waves); 2 workgroups per CU (64 KiB LDS table each)
-// Tree kernel geometry: 2 workgroups of kTreeBlock threads per CU (LDS-bound),
-// kTreeWaves waves per SIMD (VGPR budget).  Leaf launches with deep
-// per-thread subtrees (D >= kBigMinD: configs[1], configs[3]) use one
-// kTreeBlockBig-thread workgroup per CU instead, so that all 16 waves of a CU
-// share one LDS and can balance their progress (prio_step feedback form).
-constexpr int kTreeBlock = 512;
-constexpr int kTreeBlockBig = 1024;
-constexpr int kTreeBlockMax = 1024;
-constexpr uint32_t kBigMinD = 6;
-constexpr uint32_t kFeedbackMinD = 6;   // progress feedback needs enough groups per thread
-constexpr int kTreeWaves = 4;
-constexpr uint32_t kMaxD = 7;  // per-thread DFS subtree depth: 128 leaves = 2 KiB of output per thread
-constexpr uint32_t kMaxFrontierHbm = 16;  // batched Eval, HBM frontier: deepest shared level
+// Workgroup sizes, subtree depths and the frontier limit: tree_plan.hpp,
+// with the launch plans that use them.
+using dpfh::kBlock;
+using dpfh::kTreeBlock;
+using dpfh::kTreeBlockBig;
+using dpfh::kTreeBlockMax;
+using dpfh::kBigMinD;
+using dpfh::kFeedbackMinD;
+using dpfh::kTreeWaves;
+using dpfh::kMaxD;
+using dpfh::kMaxFrontierHbm;
+using dpfh::kEvalPBlock;
 
 // CU budget of the calling thread's launches (0: the whole device); see
 // cu_count() in dpf_kernels.hip.
 void set_cu_budget(int cus);
 int cu_budget();
 int cu_count();
+// The process's measurement switches (DPF_SUBTREE_DEPTH, DPF_RAW_KEYS,
+// DPF_EVAL_*) as the launch plans of tree_plan.hpp take them.
+const dpfh::TreeKnobs& tree_knobs();
 
 // Expanded-key words per key: (stop + 2) records of 8 u32.
 inline uint64_t ek_words(uint32_t stop) { return ((uint64_t)stop + 2) * 8; }

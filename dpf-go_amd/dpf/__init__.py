@@ -16,6 +16,7 @@ evaluation raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from typing import Optional, Sequence, Tuple
@@ -52,8 +53,25 @@ _u64 = ctypes.c_uint64
 _int = ctypes.c_int
 _vp = ctypes.c_void_p
 
+
+class TreeFormC(ctypes.Structure):
+    """dpf_tree_form (include/dpf_hip.h)."""
+    _fields_ = [("d", _u32), ("block", _u32), ("w", _u32), ("ltop", _u32), ("units_log", _u32), ("walk", _u32),
+                ("l1", _u32), ("uniform", ctypes.c_uint8), ("nodes", ctypes.c_uint8), ("raw", ctypes.c_uint8),
+                ("cw_lds", ctypes.c_uint8), ("feedback", ctypes.c_uint8), ("prio_small", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 2), ("nunits", _u64), ("grid", _u64), ("sub_base", _u64)]
+
+
+class EvalFormC(ctypes.Structure):
+    """dpf_eval_form (include/dpf_hip.h)."""
+    _fields_ = [("level", _u32), ("kernel", _u32), ("block", _u32), ("cw_staged", ctypes.c_uint8),
+                ("ragged", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2), ("grid", _u64), ("nodes", TreeFormC)]
+
+
 # name -> (restype, argtypes); must cover every function in include/dpf_hip.h
 SIGNATURES = {
+    "dpf_tree_form_for": (_int, [_sz, _u32, _u32, _u32, _int, ctypes.POINTER(TreeFormC)]),
+    "dpf_eval_form_for": (_int, [_sz, _sz, _u32, _sz, _int, _int, ctypes.POINTER(EvalFormC)]),
     "dpf_last_error": (ctypes.c_char_p, []),
     "dpf_key_len": (_sz, [_u32]),
     "dpf_evalfull_len": (_sz, [_u32]),
@@ -386,6 +404,39 @@ def eval_workspace_size(nkeys: int, pts_per_key: int, logN: int) -> int:
 def eval_frontier_level(logN: int, pts_per_key: int) -> int:
     """Depth of the shared frontier eval_batch_dev uses with a full workspace (0: root walks)."""
     return int(lib().dpf_eval_frontier_level(logN, pts_per_key))
+
+
+WALK_NONE, WALK_LANE, WALK_QUAD = 0, 1, 2
+EVAL_PERSIST, EVAL_PAIR_UNIFORM, EVAL_PAIR, EVAL_TRIE_KERNEL = 0, 1, 2, 3
+TreeForm = collections.namedtuple(
+    "TreeForm", "d block w ltop units_log walk l1 uniform nodes raw cw_lds feedback prio_small nunits grid sub_base")
+EvalForm = collections.namedtuple("EvalForm", "level kernel block cw_staged ragged grid nodes")
+
+
+def _tree_form(c: TreeFormC) -> "TreeForm":
+    return TreeForm(*[bool(getattr(c, f)) if f in ("uniform", "nodes", "raw", "cw_lds", "feedback", "prio_small")
+                      else int(getattr(c, f)) for f in TreeForm._fields])
+
+
+def tree_form_for(nkeys: int, logN: int, prefix_bits: int = 0, node_level: int = 0, cus: int = 0) -> "TreeForm":
+    """The form of the tree kernel (dpf_tree_form_for) that the leaf launch of
+    evalfull_subtree_dev(nkeys, logN, prefix_bits) takes (node_level = 0), or
+    the node pass down to node_level.  cus <= 0: the current device's / the
+    calling thread's stream budget.  Needs no device when cus > 0.  Describes
+    the current kernels; not a stable contract."""
+    c = TreeFormC()
+    _check(lib().dpf_tree_form_for(nkeys, logN, prefix_bits, node_level, cus, ctypes.byref(c)))
+    return _tree_form(c)
+
+
+def eval_form_for(nkeys: int, pts_per_key: int, logN: int, work_bytes: int, xs_aligned16: bool = True,
+                  cus: int = 0) -> "EvalForm":
+    """What eval_batch_dev runs for this shape, workspace size and xs alignment (dpf_eval_form_for)."""
+    c = EvalFormC()
+    _check(lib().dpf_eval_form_for(nkeys, pts_per_key, logN, work_bytes, 1 if xs_aligned16 else 0, cus,
+                                   ctypes.byref(c)))
+    return EvalForm(int(c.level), int(c.kernel), int(c.block), bool(c.cw_staged), bool(c.ragged), int(c.grid),
+                    _tree_form(c.nodes) if c.level > 0 else None)
 
 
 def eval_batch_dev(d_keys, key_len_: int, nkeys: int, d_xs, pts_per_key: int, logN: int, d_out, d_work,

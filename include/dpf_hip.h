@@ -147,6 +147,59 @@ int dpf_eval_batch_dev(int device, const uint8_t* d_keys, size_t key_len, size_t
                        size_t pts_per_key, uint32_t logN, uint8_t* d_out, void* d_work, size_t work_bytes,
                        void* stream);
 
+/* ---- Introspection: which form of a kernel a call runs -------------------
+ * The tree kernel is one source but many kernels at run time; these say which
+ * one a call takes, from the same plan (csrc/tree_plan.hpp) the launchers
+ * follow, under the process's environment switches.  They change no state and
+ * need no open device when cus > 0 (cus <= 0: the current device's CU count,
+ * or the calling thread's CU-masked stream budget).  The fields describe the
+ * current kernels for tests and tools; they are not a stable contract and may
+ * change with any release. */
+#define DPF_WALK_NONE 0 /* every thread walks from the root */
+#define DPF_WALK_LANE 1 /* shared walk, one lane per path (128-thread workgroups) */
+#define DPF_WALK_QUAD 2 /* shared walk, a quad of lanes per path (>= 256 threads) */
+typedef struct dpf_tree_form {
+    uint32_t d;         /* per-thread subtree depth */
+    uint32_t block;     /* workgroup size = 2^w */
+    uint32_t w;
+    uint32_t ltop;      /* levels walked per thread */
+    uint32_t units_log; /* threads per key = 2^units_log */
+    uint32_t walk;      /* DPF_WALK_* */
+    uint32_t l1;        /* level the shared walk ends at (0 without one) */
+    uint8_t uniform, nodes, raw, cw_lds, feedback, prio_small;
+    uint8_t pad_[2];
+    uint64_t nunits;    /* threads with work */
+    uint64_t grid;      /* workgroups */
+    uint64_t sub_base;  /* first subtree of a key, for prefix 0 */
+} dpf_tree_form;
+/* The leaf launch of dpf_evalfull_subtree_dev(nkeys, logN, prefix_bits) under
+ * the T-table back end (node_level == 0; `raw` says whether it reads the key
+ * bytes or needs expanded records), or the node pass down to level
+ * node_level below the root (prefix_bits <= node_level <= logN - 7) that the
+ * batched Eval frontier (prefix_bits = 0, node_level = L) and the byte-sliced
+ * back end run.  DPF_ERR_PARAM for a shape out of range or a grid the
+ * launcher would refuse. */
+int dpf_tree_form_for(size_t nkeys, uint32_t logN, uint32_t prefix_bits, uint32_t node_level, int cus,
+                      dpf_tree_form* form);
+#define DPF_EVAL_PERSIST 0      /* k_eval_persist: one 1024-thread workgroup per CU strides over the pairs */
+#define DPF_EVAL_PAIR_UNIFORM 1 /* k_eval2<true>: one pair per thread, a wave's queries share a key */
+#define DPF_EVAL_PAIR 2         /* k_eval2<false>: one pair per thread, per-lane keys */
+#define DPF_EVAL_TRIE_KERNEL 3  /* k_eval_trie (the experimental library, dpf_set_eval_kernel) */
+typedef struct dpf_eval_form {
+    uint32_t level;     /* frontier level L (0: root walks) */
+    uint32_t kernel;    /* DPF_EVAL_* above */
+    uint32_t block;
+    uint8_t cw_staged;  /* DPF_EVAL_PERSIST: a pair's key records sit in LDS slots */
+    uint8_t ragged;     /* the last workgroup (or stride) has threads without a pair */
+    uint8_t pad_[2];
+    uint64_t grid;
+    dpf_tree_form nodes; /* the frontier pass, when level > 0 */
+} dpf_eval_form;
+/* What dpf_eval_batch_dev runs for nkeys x pts_per_key queries with a
+ * workspace of work_bytes and a d_xs that is (or is not) 16-byte aligned. */
+int dpf_eval_form_for(size_t nkeys, size_t pts_per_key, uint32_t logN, size_t work_bytes, int xs_aligned16, int cus,
+                      dpf_eval_form* form);
+
 /* ---- CU-partitioned streams (no reference counterpart: engine plumbing) -
  * A stream whose kernels may run only on CUs [cu_first, cu_first+cu_count)
  * of `device` (hipExtStreamCreateWithCUMask).  Bit i of the mask is spread

@@ -186,6 +186,9 @@ def test_cu_masked_stream_big_tree_workgroups():
     S = dpf.stream_create_cu_masked(0, 16)
     try:
         logN, nk = 20, 512
+        f = dpf.tree_form_for(nk, logN, cus=16)
+        assert (f.d, f.block, f.feedback, f.uniform, f.raw) == (7, 1024, True, True, True), f
+        assert f.grid == nk * 64 // 1024 > 16, f             # several rounds of them on the 16 CUs
         al, s0, s1 = synth.key_seeds(nk, logN, first=2626)
         ka, _ = dpf.gen_batch_seeded(al, logN, s0, s1)
         kl, ol = dpf.key_len(logN), dpf.evalfull_len(logN)

@@ -86,15 +86,33 @@ def test_config1_every_byte_vs_oracle(cfg1, aes, share):
     assert np.array_equal(got, want[share]), _first_diff(got, want[share])
 
 
-@pytest.mark.parametrize("nk", [2056, 4100])
+@pytest.mark.parametrize("nk", [2056, 4100, 2052])
 def test_big_workgroups_with_a_ragged_last_one(nk):
     """r06: leaf launches with deep subtrees run 1024-thread workgroups whose
     waves steer their priority by the progress of the other waves of their
-    SIMD (LDS slots, dpf_kernels.hip prio_by_lead).  At 2056 / 4100 keys the
-    grid's last workgroup is half full: its missing waves never publish
-    progress, the others must neither wait on them nor write past the batch.
-    Every byte against the oracle."""
+    SIMD (LDS slots, dpf_kernels.hip prio_by_lead).  At 2056 / 2052 keys the
+    grid's last workgroup is half / a quarter full: its missing waves never
+    publish progress, the others must neither wait on them nor write past the
+    batch.  Every byte against the oracle.  The plan (dpf.tree_form_for) says
+    so: 1024-thread feedback workgroups of raw keys, the last one holding 8
+    (2056 keys) or 4 (2052 keys) of its 16 waves.
+    4100 keys were meant as the quarter-full case, and the plan shows that
+    they never were: on 256 CUs their 262400 threads at D = 7 are just past
+    one round of 16 waves per CU, so the model takes D = 4 (512-thread
+    one-key workgroups, the quad walk, 4100 whole workgroups, no feedback).
+    The case stays as the parity check of that two-round shape."""
     logN = 20
+    import torch
+    f = dpf.tree_form_for(nk, logN, cus=256)          # the shapes above are those of a 256-CU device
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert dpf.tree_form_for(nk, logN) == f       # ... which this run takes
+    if nk != 4100:
+        assert (f.d, f.block, f.uniform, f.raw, f.feedback, f.walk) == (7, 1024, True, True, True, dpf.WALK_NONE), f
+        assert f.nunits == nk * 64 and f.grid == nk * 64 // 1024 + 1, f
+        assert f.nunits % f.block == {2056: 512, 2052: 256}[nk], f
+    else:
+        assert (f.d, f.block, f.uniform, f.raw, f.feedback, f.walk) == (4, 512, True, True, False, dpf.WALK_QUAD), f
+        assert f.cw_lds and f.nunits == nk * 512 and f.grid == nk, f
     al, s0, s1 = synth.key_seeds(nk, logN, first=31337)
     ka, _ = dpf.gen_batch_seeded(al, logN, s0, s1)
     got = _dev_evalfull(ka, logN)

@@ -340,6 +340,15 @@ import numpy as np, dpf, oracle
 from dpf import synth
 assert dpf.gpu_init(1) >= 1
 dpf.set_small_call_path("gpu")
+import os
+D, RAW = int(os.environ["DPF_SUBTREE_DEPTH"]), os.environ.get("DPF_RAW_KEYS") != "0"
+for nk, logN in ((1, 24), (70, 16)):          # the plan reports the forced depth, for both shapes
+    f = dpf.tree_form_for(nk, logN)
+    assert f.d == D and f.ltop == logN - 7 - D and f.nunits == nk << f.ltop, f
+    assert f.uniform == (f.ltop >= 6) and f.raw == (RAW and f.uniform), f
+ws = dpf.eval_workspace_size(70, 256, 16)
+e = dpf.eval_form_for(70, 256, 16, ws)
+assert e.level == 7 and e.kernel == dpf.EVAL_PERSIST and e.nodes.d == min(D, 7) and e.nodes.nodes, e
 def keys(nk, logN, first):
     al, s0, s1 = synth.key_seeds(nk, logN, first=first)
     return (al,) + tuple(dpf.gen_batch_seeded(al, logN, s0, s1))
@@ -363,27 +372,16 @@ def test_every_subtree_depth(depth, raw):
     """Every per-thread subtree depth D of the tree kernel (DPF_SUBTREE_DEPTH=D),
     from raw key bytes and (DPF_RAW_KEYS=0) from expanded records, both
     shares against the oracle byte for byte.  A fresh child per case: the two
-    switches are read once per process.  The shapes are the smallest that
-    reach every form of k_evalfull on a 256-CU device (pick_shape /
-    pick_block evaluated on the host):
-
-      EvalFull, 1 key, logN 24 (stop 17): one-key workgroups, CWs from LDS
-        D   threads  workgroup  shared walk
-        0   131072   512        one quad of lanes per path (W = 9)
-        1    65536   256        one quad of lanes per path (W = 8)
-        2    32768   128        one lane per path (W = 7)
-        3+   16384..1024  64    none
-      EvalFull, 70 keys, logN 16 (stop 9)
-        0    35840   256        quad; two workgroups per key
-        1    17920   128        one lane per path
-        2, 3  8960, 4480  64    none; wave-uniform keys, one wave per workgroup
-        4..7  2240..280   64    none; 32..4 threads per key: per-lane keys
-      Eval, 70 keys x 256 points, logN 16: node pass to level 7 (depth min(D, 7)),
-        128..1 threads per key (wave-uniform for D <= 1), then the persistent
-        walk kernel; every key's alpha is among its points.
-
-    Raw key bytes are read where stop - D >= 6 (all of the 1-key case, D <= 3
-    of the 70-key case), expanded records elsewhere and in the node pass."""
+    switches are read once per process.  The shapes: EvalFull of 1 key at
+    logN 24 (one-key workgroups, correction words from LDS, every shared walk)
+    and of 70 keys at logN 16 (wave-uniform and per-lane keys), and Eval of 70
+    keys x 256 points at logN 16 (node pass to level 7 at depth min(D, 7),
+    then the persistent walk kernel; every key's alpha is among its points).
+    Threads, workgroup and walk kind of each on a 256-CU device, and where raw
+    key bytes are read, are recorded per D in tests/c/tree_plan_test.cpp
+    (tests/test_tree_plan_cpu.py), and the child asserts that the plan
+    (dpf.tree_form_for) reports the forced depth for both shapes.  The forms
+    the unforced paths reach are run by tests/test_gpu_tree_forms.py."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
