@@ -10,7 +10,8 @@
 // own: stage_plan.hpp cuts a host-buffer call into the chunks of the staging
 // pipeline (chunk sizes, subtree slabs, output offsets), copy_pool.hpp is the
 // thread pool of the pinned <-> caller-buffer copies, pir_update_plan.hpp
-// plans dpf_pir_db_update / _read.  This file keeps the HIP calls: buffers,
+// plans dpf_pir_db_update / _read, eval_bits_plan.hpp (with tree_plan.hpp, by
+// way of the launchers) the Eval into selection bits.  This file keeps the HIP calls: buffers,
 // streams, events and launches, and the argument checks of the entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -768,6 +769,56 @@ int dpf_eval_batch_dev(int device, const uint8_t* d_keys, size_t klen, size_t nk
     return DPF_OK;
 }
 
+size_t dpf_eval_bits_stride(size_t npts) { return dpfh::eval_bits_stride(npts); }
+
+size_t dpf_eval_bits_workspace_size(size_t nkeys, size_t npts, uint32_t logN) {
+    return dpf_eval_workspace_size(nkeys, npts, logN);
+}
+
+// Every argument check of dpf_eval_bits_dev, in the order it reports; no
+// device call.
+static int check_eval_bits(const void* d_keys, size_t klen, size_t nkeys, const void* d_xs, size_t npts, uint32_t logN,
+                           const void* d_bits, size_t bits_stride, const void* d_work, size_t work_bytes) {
+    if (int rc = check_key(klen, logN, false)) return rc;
+    if (bits_stride % 16 != 0 || bits_stride < dpfh::eval_bits_stride(npts))
+        return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16, at least dpf_eval_bits_stride(npts)");
+    if ((uintptr_t)d_xs % 8 != 0 || ((uintptr_t)d_bits | (uintptr_t)d_work) % 16 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys == 0 || npts == 0) return DPF_OK;
+    if (!d_keys || !d_xs || !d_bits || !d_work) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (work_bytes < nkeys * dpfk::ek_words(stop_of(logN)) * 4)
+        return fail(DPF_ERR_PARAM, "dpf: Eval workspace too small");
+    return DPF_OK;
+}
+
+// The launches of dpf_eval_bits_dev, arguments checked: the caller holds the
+// device and CU scopes.
+static hipError_t eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, const uint64_t* d_xs, size_t npts,
+                                   uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
+                                   hipStream_t st) {
+    const uint32_t stop = stop_of(logN);
+    const size_t ekb = pir_ek_bytes(nkeys, logN);
+    forget_expanded(d_work);
+    hipError_t e = dpfk::launch_unpack(d_keys, klen, nkeys, stop, (uint32_t*)d_work, st);
+    if (e != hipSuccess) return e;
+    void* frontier = work_bytes > ekb ? (uint8_t*)d_work + ekb : nullptr;
+    return dpfk::launch_eval_bits((const uint32_t*)d_work, stop, logN, d_xs, nkeys, npts, d_bits, bits_stride, frontier,
+                                  work_bytes > ekb ? work_bytes - ekb : 0, st);
+}
+
+int dpf_eval_bits_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, const uint64_t* d_xs, size_t npts,
+                      uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
+                      void* stream) {
+    if (int rc = check_eval_bits(d_keys, klen, nkeys, d_xs, npts, logN, d_bits, bits_stride, d_work, work_bytes))
+        return rc;
+    if (nkeys == 0 || npts == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_xs, npts, logN, d_bits, bits_stride, d_work, work_bytes,
+                             (hipStream_t)stream));
+    return DPF_OK;
+}
+
 // Introspection: the launchers' own plans (tree_plan.hpp) as plain C structs.
 static dpf_tree_form c_form(const dpfh::TreeForm& t) {
     dpf_tree_form f;
@@ -1255,6 +1306,74 @@ int dpf_pir_write_sliced_any_dev(int device, const uint8_t* d_keys, size_t klen,
 
 size_t dpf_xor_fold_workspace_size(void) { return dpfk::pir_fold_parts_bytes(); }
 
+// ---- PIR over a sparse key set: record j lives at domain point d_points[j] ----
+// The selection bits come from dpf_eval_bits_dev at the records' points, not
+// from an EvalFull of a subtree; the fold and the scatter are the dense ones.
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// d_work of the two sparse composites: [Eval-bits workspace | bit rows
+// [nkeys][dpf_eval_bits_stride(nrec)] | the fold's partials], each part
+// rounded up to 16 bytes.
+struct SparseWs {
+    size_t eval_bytes, stride;
+    uint8_t* bits;
+    uint32_t* parts;
+};
+static SparseWs sparse_ws(void* d_work, size_t nkeys, uint64_t nrec, uint32_t logN) {
+    SparseWs w;
+    w.eval_bytes = align16(dpf_eval_bits_workspace_size(nkeys, nrec, logN));
+    w.stride = dpf_eval_bits_stride(nrec);
+    w.bits = (uint8_t*)d_work + w.eval_bytes;
+    w.parts = (uint32_t*)(w.bits + align16(nkeys * w.stride));
+    return w;
+}
+
+size_t dpf_pir_sparse_workspace_size(size_t nkeys, uint64_t nrec, uint32_t logN) {
+    return align16(dpf_eval_bits_workspace_size(nkeys, nrec, logN)) + align16(nkeys * dpf_eval_bits_stride(nrec)) +
+           align16(dpf_xor_fold_workspace_size());
+}
+
+int dpf_pir_answer_sparse_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                              const uint64_t* d_points, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                              uint8_t* d_ans, void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes, true)) return rc;
+    if (int rc = check_key(klen, logN, false)) return rc;
+    if (int rc = check_pir_bufs(d_keys, nkeys, d_dbs, nrec, d_ans, d_work)) return rc;
+    if (nkeys > 0 && nrec > 0 && !d_points) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if ((uintptr_t)d_points % 8 != 0) return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        return DPF_OK;
+    }
+    const SparseWs w = sparse_ws(d_work, nkeys, nrec, logN);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
+    HIP_TRY(dpfk::launch_pir_fold_sliced((const uint32_t*)w.bits, w.stride / 4, d_dbs, nrec, rec_bytes, (uint32_t)nkeys,
+                                         (uint32_t*)d_ans, w.parts, st));
+    return DPF_OK;
+}
+
+int dpf_pir_write_sparse_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
+                             const uint64_t* d_points, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec,
+                             size_t rec_bytes, void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(rec_bytes, true)) return rc;
+    if (int rc = check_key(klen, logN, false)) return rc;
+    if (!d_keys || !d_points || !d_msgs || !d_dbs || !d_work) return fail(DPF_ERR_PARAM, "dpf: null device buffer");
+    if (((uintptr_t)d_msgs | (uintptr_t)d_dbs | (uintptr_t)d_work) % 16 != 0 || (uintptr_t)d_points % 8 != 0)
+        return fail(DPF_ERR_PARAM, "dpf: misaligned device buffer");
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    const SparseWs w = sparse_ws(d_work, nkeys, nrec, logN);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
+    HIP_TRY(dpfk::launch_scatter_sliced((const uint32_t*)w.bits, w.stride / 4, d_dbs, nrec, rec_bytes, d_msgs, nkeys, st));
+    return DPF_OK;
+}
+
 int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block) {
     dpfk::set_fold_limits(max_blocks, max_sg_per_block);
     return DPF_OK;
@@ -1271,10 +1390,18 @@ struct PirDb {
     DevList devs;                  // per shard: its device
     std::vector<void*> shard;      // per device: its DB slice
     std::vector<uint64_t> shard_n; // records in that slice
+    // The sparse kind (dpf_pir_db_create_sparse): record j lives at domain
+    // point points[j]; shard g holds records [g * shard_cap, ...), a range of
+    // whole super-groups and not a subtree (pbits = 0), with its slice of the
+    // points beside it in HBM.
+    bool sparse = false;
+    uint64_t shard_cap = 0;
+    std::vector<void*> shard_pts;  // per device: uint64 points of its records
     ~PirDb() {
         for (size_t i = 0; i < shard.size(); ++i) {
             DeviceGuard gd(devs[i]->id);
             (void)hipFree(shard[i]);
+            if (i < shard_pts.size()) (void)hipFree(shard_pts[i]);
         }
     }
 };
@@ -1303,9 +1430,11 @@ static hipError_t copy_rows_down(uint8_t* host, const void* dev, size_t pitch, s
 }
 
 // any: dpf_pir_db_create_any (every width from 1 byte; shards at w4 bytes per
-// record); else dpf_pir_db_create_wide's rule.
+// record); else dpf_pir_db_create_wide's rule.  sparse: dpf_pir_db_create_sparse
+// (record j at domain point points[j]; shards are record ranges of whole
+// super-groups, any device count, each with its points beside it).
 static int pir_db_create(const uint8_t* db, uint64_t nrec, size_t caller_bytes, uint32_t logN, int ngpus, void** handle,
-                         bool any) {
+                         bool any, bool sparse = false, const uint64_t* points = nullptr) {
     if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
     *handle = nullptr;
     if (any) {
@@ -1315,14 +1444,22 @@ static int pir_db_create(const uint8_t* db, uint64_t nrec, size_t caller_bytes, 
         return rc;
     }
     const size_t rec_bytes = (caller_bytes + 3) & ~(size_t)3;   // on the device
-    if (logN > 63 || (logN < 64 && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: DB larger than 2^logN");
+    if (logN > 63 || (!sparse && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: DB larger than 2^logN");
+    if (sparse) {
+        if (nrec > 0 && (!points || !db)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+        for (uint64_t j = 0; j < nrec; ++j)
+            if ((points[j] >> logN) != 0) return fail(DPF_ERR_PARAM, "dpf: point outside the 2^logN domain");
+    }
     int have = 0;
     const DevList devs = pick_devs(0, &have);
     if (have <= 0) return have;
     const int want = ngpus <= 0 ? have : ngpus;
     uint32_t pb = 0;
-    if (want > have || !dpfh::gpus_to_pb(want, stop_of(logN), &pb))
+    if (sparse) {
+        if (want > have) return fail(DPF_ERR_PARAM, "dpf: ngpus must be <= opened devices");
+    } else if (want > have || !dpfh::gpus_to_pb(want, stop_of(logN), &pb)) {
         return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= opened devices and 2^(logN-7)");
+    }
     auto h = std::make_unique<PirDb>();
     h->logN = logN;
     h->pbits = pb;
@@ -1337,7 +1474,10 @@ static int pir_db_create(const uint8_t* db, uint64_t nrec, size_t caller_bytes, 
     h->sliced = !lds;
     if (lds && caller_bytes % 32 != 0)
         return fail(DPF_ERR_PARAM, "dpf: row-major shards (DPF_PIR_FOLD=lds) take multiples of 32 bytes only");
-    const uint64_t slice = 1ull << (logN - pb);
+    if (lds && sparse) return fail(DPF_ERR_PARAM, "dpf: sparse handles keep sliced shards only (DPF_PIR_FOLD=lds set)");
+    h->sparse = sparse;
+    h->shard_cap = sparse ? ((nrec + 255) / 256 + (uint64_t)want - 1) / (uint64_t)want * 256 : 0;
+    const uint64_t slice = sparse ? h->shard_cap : 1ull << (logN - pb);
     for (int g = 0; g < want; ++g) {
         const uint64_t lo = std::min<uint64_t>(nrec, (uint64_t)g * slice);
         const uint64_t hi = std::min<uint64_t>(nrec, lo + slice);
@@ -1349,6 +1489,14 @@ static int pir_db_create(const uint8_t* db, uint64_t nrec, size_t caller_bytes, 
         h->devs.push_back(devs[(size_t)g]);     // ~PirDb frees what was allocated so far
         h->shard.push_back(p);
         h->shard_n.push_back(hi - lo);
+        if (sparse) {
+            void* q = nullptr;
+            if (hipMalloc(&q, std::max<uint64_t>(hi - lo, 2) * 8) != hipSuccess)
+                return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
+            h->shard_pts.push_back(q);
+            if (hi > lo && hipMemcpy(q, points + lo, (hi - lo) * 8, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(DPF_ERR_HIP, "dpf: DB upload failed");
+        }
         if (hi <= lo) continue;
         if (!h->sliced) {
             if (hipMemcpy(p, db + lo * rec_bytes, (hi - lo) * rec_bytes, hipMemcpyHostToDevice) != hipSuccess)
@@ -1387,6 +1535,11 @@ int dpf_pir_db_create_any(const uint8_t* db, uint64_t nrec, size_t rec_bytes, ui
     return pir_db_create(db, nrec, rec_bytes, logN, ngpus, handle, true);
 }
 
+int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN,
+                             int ngpus, void** handle) {
+    return pir_db_create(db, nrec, rec_bytes, logN, ngpus, handle, true, true, points);
+}
+
 int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, uint8_t* ans) {
     PirDb* h = (PirDb*)handle;
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
@@ -1400,13 +1553,18 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
         std::lock_guard<std::mutex> lk(d.mu);
         DeviceGuard gd(d.id);
         HIP_TRY(d.keys.ensure(std::max<size_t>(1, nkeys * klen)));
-        HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+        HIP_TRY(d.work.ensure(h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[lo], h->logN)
+                                        : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
         HIP_TRY(d.out.ensure(std::max<size_t>(32, nkeys * w4)));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
         // (Row-major shards are multiples of 32 bytes; sliced ones any multiple of 4.)
-        int r = (h->sliced ? dpf_pir_answer_sliced_any_dev : dpf_pir_answer_wide_dev)(
-            d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)h->shard[lo],
-            h->shard_n[lo], w4, (uint8_t*)d.out.p, d.work.p, d.st);
+        int r = h->sparse
+                    ? dpf_pir_answer_sparse_dev(d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN,
+                                                (const uint64_t*)h->shard_pts[lo], (const uint8_t*)h->shard[lo],
+                                                h->shard_n[lo], w4, (uint8_t*)d.out.p, d.work.p, d.st)
+                    : (h->sliced ? dpf_pir_answer_sliced_any_dev : dpf_pir_answer_wide_dev)(
+                          d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo,
+                          (const uint8_t*)h->shard[lo], h->shard_n[lo], w4, (uint8_t*)d.out.p, d.work.p, d.st);
         if (r) return r;
         HIP_TRY(copy_rows_down(part[lo].data(), d.out.p, w4, rb, nkeys, d.st));
         HIP_TRY(hipStreamSynchronize(d.st));
@@ -1476,7 +1634,8 @@ static int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const
     if (n == 0) return DPF_OK;
     if (!idx || (!recs && !out)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
     dpfh::PirUpdatePlan plan;
-    if (!dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan))
+    if (!(h->sparse ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->shard_cap, h->shard.size(), recs != nullptr, &plan)
+                    : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
         return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
     const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->w4);
     std::vector<uint8_t> host;
@@ -1514,13 +1673,18 @@ int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkey
         std::lock_guard<std::mutex> lk(d.mu);
         DeviceGuard gd(d.id);
         HIP_TRY(d.keys.ensure(nkeys * klen));
-        HIP_TRY(d.work.ensure(dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+        HIP_TRY(d.work.ensure(h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[lo], h->logN)
+                                        : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
         HIP_TRY(d.out.ensure(nkeys * w4));
         HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
         HIP_TRY(copy_rows_up(d.out.p, w4, msgs, rb, nkeys, d.st));   // zero pad bytes: the DB's stay zero
-        int r = (h->sliced ? dpf_pir_write_sliced_any_dev : dpf_pir_write_wide_dev)(
-            d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)d.out.p,
-            (uint8_t*)h->shard[lo], h->shard_n[lo], w4, d.work.p, d.st);
+        int r = h->sparse
+                    ? dpf_pir_write_sparse_dev(d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN,
+                                               (const uint64_t*)h->shard_pts[lo], (const uint8_t*)d.out.p,
+                                               (uint8_t*)h->shard[lo], h->shard_n[lo], w4, d.work.p, d.st)
+                    : (h->sliced ? dpf_pir_write_sliced_any_dev : dpf_pir_write_wide_dev)(
+                          d.id, (const uint8_t*)d.keys.p, klen, nkeys, h->logN, h->pbits, lo, (const uint8_t*)d.out.p,
+                          (uint8_t*)h->shard[lo], h->shard_n[lo], w4, d.work.p, d.st);
         if (r) return r;
         HIP_TRY(hipStreamSynchronize(d.st));
         return (int)DPF_OK;

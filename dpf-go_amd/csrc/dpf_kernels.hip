@@ -553,6 +553,57 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
     if (q0 < nq) eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, q0, p);
 }
 
+// Eval of every key at one shared list of points, the answers as packed
+// selection bits: bit j % 8 of byte j / 8 of row `key` of bits[][bits_stride]
+// is Eval(key, xs[j]), EvalFull's bit order, so the rows feed the folds and
+// the scatter as EvalFull output does.  The mapping, the tail rule and what
+// the launch guarantees are written down in eval_bits_plan.hpp: wave w owns
+// unit w % units (128 points) of key w / units; lane l walks points 128 u + l
+// and 128 u + 64 + l in lockstep (the pair walk of k_eval2<true>: the key is
+// wave-uniform at every npts, its records come by scalar loads); a lane past
+// npts reads point npts - 1 and is masked out of the ballot; the two ballots
+// are the unit's 16 bytes, stored by lane 0 as one vector store.  No per-key
+// copy of the points, no byte per query, no atomics.
+// (A batch would need 2^32 keys before the 32-bit readfirstlane of the key
+// index, here and in pair_key, could truncate: their records alone are 256 GiB.)
+__global__ __launch_bounds__(kBlock, 4) void k_eval_bits(const uint32_t* __restrict__ ekeys, uint32_t stop,
+                                                         uint32_t logN, const uint64_t* __restrict__ xs, uint64_t npts,
+                                                         uint64_t units, uint64_t nwaves,
+                                                         const uint4* __restrict__ fseed,
+                                                         const uint8_t* __restrict__ ft, uint32_t L,
+                                                         uint8_t* __restrict__ bits, uint64_t bits_stride) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_tab[kTabWords];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wib;   // wave-uniform
+    const bool live = w < nwaves;
+    uint64_t key = 0, unit = 0, j0 = 0, j1 = 0;
+    // The points and frontier nodes are requested before the table fill, as in k_eval2.
+    PairIn p{};
+    if (live) {
+        key = w / units;
+        unit = w - key * units;
+        j0 = dpfh::eval_bits_point(unit, lane, 0);
+        j1 = dpfh::eval_bits_point(unit, lane, 1);
+        const uint32_t* ek = ekeys + key * ((uint64_t)(stop + 2) * 8);
+        p.x0 = xs[dpfh::eval_bits_clamp(j0, npts)];
+        p.x1 = xs[dpfh::eval_bits_clamp(j1, npts)];
+        p.n0 = eval_start(ek, key, p.x0, logN, fseed, ft, L);
+        p.n1 = eval_start(ek, key, p.x1, logN, fseed, ft, L);
+    }
+    fill_table(s_tab);
+    __builtin_amdgcn_s_setprio(3);
+    if (!live) return;
+    // eval_pair_bits<true> names its key as query / pts_per_key: query `key`
+    // of a batch with one point per key.
+    const uint32_t b = eval_pair_bits<true>(ekeys, stop, logN, key + 1, 1, fseed, L, s_tab, key, p);
+    const uint64_t m0 = __builtin_amdgcn_ballot_w64((b & 1u) != 0 && j0 < npts);
+    const uint64_t m1 = __builtin_amdgcn_ballot_w64(((b >> 8) & 1u) != 0 && j1 < npts);
+    if (lane == 0)
+        *reinterpret_cast<uint4*>(bits + key * bits_stride + dpfh::eval_bits_unit_off(unit)) =
+            make_uint4((uint32_t)m0, (uint32_t)(m0 >> 32), (uint32_t)m1, (uint32_t)(m1 >> 32));
+}
+
 // Persistent batched Eval (r05): one 1024-thread workgroup per CU fills its
 // T-table once and strides over the query pairs; the next pair's points and
 // frontier nodes move into per-wave LDS slots by LDS-DMA
@@ -912,6 +963,31 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
         hipLaunchKernelGGL(k_eval2<true>, grid, block, 0, st, ek, stop, logN, xs, nq, pts_per_key, fseed, ft, L, out);
     else
         hipLaunchKernelGGL(k_eval2<false>, grid, block, 0, st, ek, stop, logN, xs, nq, pts_per_key, fseed, ft, L, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_bits(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nkeys,
+                            uint64_t npts, uint8_t* bits, uint64_t bits_stride, void* frontier,
+                            uint64_t frontier_bytes, hipStream_t st) {
+    if (nkeys == 0 || npts == 0) return hipSuccess;
+    // The whole choice (frontier level, block, grid, units) is dpfh::eval_bits_form's.
+    dpfh::EvalBitsForm f;
+    if (!dpfh::eval_bits_form(nkeys, npts, stop, logN, frontier == nullptr ? 0 : frontier_bytes, (uint64_t)cu_count(),
+                              tree_knobs(), &f))
+        return hipErrorInvalidValue;
+    if (bits_stride % 16 != 0 || bits_stride < dpfh::eval_bits_stride(npts)) return hipErrorInvalidValue;
+    const uint4* fseed = nullptr;
+    const uint8_t* ft = nullptr;
+    if (f.L > 0) {
+        uint8_t* fs = static_cast<uint8_t*>(frontier);
+        uint8_t* fts = fs + (nkeys << f.L) * 16;
+        hipError_t e = launch_tree<true>(ek, nkeys, stop, f.L, 0, 0, fs, fts, 1ull << f.L, st);
+        if (e != hipSuccess) return e;
+        fseed = reinterpret_cast<const uint4*>(fs);
+        ft = fts;
+    }
+    hipLaunchKernelGGL(k_eval_bits, dim3((uint32_t)f.grid), dim3(f.block), 0, st, ek, stop, logN, xs, (uint64_t)npts,
+                       f.units, f.nwaves, fseed, ft, f.L, bits, bits_stride);
     return hipGetLastError();
 }
 

@@ -14,7 +14,8 @@ namespace dpfh {
 constexpr size_t kPlanRadixMin = 4096;   // entries from which the planner sorts by radix
 
 // Entries [shard_off[s], shard_off[s + 1]) belong to shard s (2^pbits shards,
-// a record's shard is idx >> (logN - pbits)); within a shard `local` (the
+// a record's shard is idx >> (logN - pbits); a sparse handle's shards are
+// record ranges, plan_pir_update_ranges); within a shard `local` (the
 // index inside the shard) is non-decreasing.  src[k] is the position in the
 // caller's arrays that entry k came from.
 struct PirUpdatePlan {
@@ -23,13 +24,11 @@ struct PirUpdatePlan {
     std::vector<size_t> shard_off;
 };
 
-// Plans n caller indices for a DB of nrec <= 2^logN records over 2^pbits
-// shards (pbits <= logN <= 63).  Returns false, with *plan untouched, if any
-// index is >= nrec.  The entries are stably sorted by index; with keep_last
-// only the last occurrence of each index stays (an update: the last wins),
-// without it every entry stays (a read: duplicates are answered twice).
-inline bool plan_pir_update(const uint64_t* idx, size_t n, uint64_t nrec, uint32_t logN, uint32_t pbits, bool keep_last,
-                            PirUpdatePlan* plan) {
+// The planner behind both shardings below: split(v, &shard, &local) places
+// index v (shards ascending with v), nshards of them.
+template <class Split>
+inline bool plan_pir_update_split(const uint64_t* idx, size_t n, uint64_t nrec, size_t nshards, bool keep_last,
+                                  Split split, PirUpdatePlan* plan) {
     for (size_t i = 0; i < n; ++i)
         if (idx[i] >= nrec) return false;
     // (index, position) pairs in index order, equal indices in the caller's
@@ -65,22 +64,52 @@ inline bool plan_pir_update(const uint64_t* idx, size_t n, uint64_t nrec, uint32
             e.swap(tmp);
         }
     }
-    const uint32_t shift = logN - pbits;
-    const uint64_t mask = (1ull << shift) - 1;
     PirUpdatePlan p;
-    p.shard_off.assign(((size_t)1 << pbits) + 1, 0);
+    p.shard_off.assign(nshards + 1, 0);
     p.local.reserve(n);
     p.src.reserve(n);
     for (size_t k = 0; k < n; ++k) {
         const uint64_t v = e[k].v;
         if (keep_last && k + 1 < n && e[k + 1].v == v) continue;
-        p.local.push_back(v & mask);
+        size_t shard = 0;
+        uint64_t local = 0;
+        split(v, &shard, &local);
+        p.local.push_back(local);
         p.src.push_back(e[k].pos);
-        ++p.shard_off[(size_t)(v >> shift) + 1];
+        ++p.shard_off[shard + 1];
     }
     for (size_t s = 1; s < p.shard_off.size(); ++s) p.shard_off[s] += p.shard_off[s - 1];
     *plan = std::move(p);
     return true;
+}
+
+// Plans n caller indices for a DB of nrec <= 2^logN records over 2^pbits
+// shards (pbits <= logN <= 63).  Returns false, with *plan untouched, if any
+// index is >= nrec.  The entries are stably sorted by index; with keep_last
+// only the last occurrence of each index stays (an update: the last wins),
+// without it every entry stays (a read: duplicates are answered twice).
+inline bool plan_pir_update(const uint64_t* idx, size_t n, uint64_t nrec, uint32_t logN, uint32_t pbits, bool keep_last,
+                            PirUpdatePlan* plan) {
+    const uint32_t shift = logN - pbits;
+    const uint64_t mask = (1ull << shift) - 1;
+    return plan_pir_update_split(idx, n, nrec, (size_t)1 << pbits, keep_last,
+                                 [=](uint64_t v, size_t* shard, uint64_t* local) {
+                                     *shard = (size_t)(v >> shift);
+                                     *local = v & mask;
+                                 },
+                                 plan);
+}
+
+// The same for a sparse handle: shard s holds the records [s * cap, (s + 1) *
+// cap) of the list (cap > 0 whenever nrec > 0), nshards of them.
+inline bool plan_pir_update_ranges(const uint64_t* idx, size_t n, uint64_t nrec, uint64_t cap, size_t nshards,
+                                   bool keep_last, PirUpdatePlan* plan) {
+    return plan_pir_update_split(idx, n, nrec, nshards, keep_last,
+                                 [=](uint64_t v, size_t* shard, uint64_t* local) {
+                                     *shard = (size_t)(v / cap);
+                                     *local = v % cap;
+                                 },
+                                 plan);
 }
 
 }  // namespace dpfh

@@ -95,6 +95,13 @@ SIGNATURES = {
     "dpf_eval_workspace_size": (_sz, [_sz, _sz, _u32]),
     "dpf_eval_frontier_level": (_u32, [_u32, _sz]),
     "dpf_eval_batch_dev": (_int, [_int, _vp, _sz, _sz, _vp, _sz, _u32, _vp, _vp, _sz, _vp]),
+    "dpf_eval_bits_stride": (_sz, [_sz]),
+    "dpf_eval_bits_workspace_size": (_sz, [_sz, _sz, _u32]),
+    "dpf_eval_bits_dev": (_int, [_int, _vp, _sz, _sz, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp]),
+    "dpf_pir_sparse_workspace_size": (_sz, [_sz, _u64, _u32]),
+    "dpf_pir_answer_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_write_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_create_sparse": (_int, [_u64p, _u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_expand_keys_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp]),
     "dpf_evalfull_expanded_dev": (_int, [_int, _vp, _sz, _u32, _u32, _u64, _vp, _vp]),
     "dpf_forget_workspace": (_int, [_vp]),
@@ -447,6 +454,27 @@ def eval_batch_dev(d_keys, key_len_: int, nkeys: int, d_xs, pts_per_key: int, lo
                                     _ptr(d_out), _ptr(d_work), nbytes, _stream_handle(stream)))
 
 
+def eval_bits_stride(npts: int) -> int:
+    """Bytes of a bit row eval_bits_dev writes: 16 * ceil(npts / 128)."""
+    return int(lib().dpf_eval_bits_stride(npts))
+
+
+def eval_bits_workspace_size(nkeys: int, npts: int, logN: int) -> int:
+    """Expanded keys plus the frontier (eval_workspace_size); nothing that grows as nkeys * npts."""
+    return int(lib().dpf_eval_bits_workspace_size(nkeys, npts, logN))
+
+
+def eval_bits_dev(d_keys, key_len_: int, nkeys: int, d_xs, npts: int, logN: int, d_bits, bits_stride: int, d_work,
+                  device: int = 0, stream=None) -> None:
+    """Every key at the npts shared points d_xs (uint64), as selection-bit
+    rows d_bits[nkeys][bits_stride]: bit j % 8 of byte j / 8 of row k is
+    Eval(key_k, d_xs[j]) (dpf_eval_bits_dev).  d_work's size picks root walks
+    or a shared frontier, as for eval_batch_dev."""
+    nbytes = int(d_work.numel() * d_work.element_size())
+    _check(lib().dpf_eval_bits_dev(device, _ptr(d_keys), key_len_, nkeys, _ptr(d_xs), npts, logN, _ptr(d_bits),
+                                   bits_stride, _ptr(d_work), nbytes, _stream_handle(stream)))
+
+
 def expand_keys_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_work, device: int = 0, stream=None) -> None:
     _check(lib().dpf_expand_keys_dev(device, _ptr(d_keys), key_len_, nkeys, logN, _ptr(d_work),
                                      _stream_handle(stream)))
@@ -742,6 +770,26 @@ def pir_write_sliced_any_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_msg
                                               _stream_handle(stream)))
 
 
+# ---- PIR over a sparse key set: record j lives at domain point d_points[j] ----
+def pir_sparse_workspace_size(nkeys: int, nrec: int, logN: int) -> int:
+    return int(lib().dpf_pir_sparse_workspace_size(nkeys, nrec, logN))
+
+
+def pir_answer_sparse_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_points, d_dbs, nrec: int, rec_bytes: int,
+                          d_ans, d_work, device: int = 0, stream=None) -> None:
+    """Server answers (nkeys x rec_bytes): the XOR of the records j of the
+    sliced DB (any multiple of 4 bytes) with Eval(key, d_points[j]) = 1."""
+    _check(lib().dpf_pir_answer_sparse_dev(device, _ptr(d_keys), key_len_, nkeys, logN, _ptr(d_points), _ptr(d_dbs),
+                                           nrec, rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_write_sparse_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_points, d_msgs, d_dbs, nrec: int,
+                         rec_bytes: int, d_work, device: int = 0, stream=None) -> None:
+    """The dual: record j ^= XOR of the messages d_msgs[k] of the keys with Eval(key_k, d_points[j]) = 1."""
+    _check(lib().dpf_pir_write_sparse_dev(device, _ptr(d_keys), key_len_, nkeys, logN, _ptr(d_points), _ptr(d_msgs),
+                                          _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work), _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -755,9 +803,16 @@ class PirDB:
     whatever the array's shape; widths that are not a multiple of 32 go
     through dpf_pir_db_create_any) resident in HBM, sharded by top-level subtree over
     ngpus GPUs; answer() returns each key's XOR-inner-product, (n, rec_bytes)
-    (host XOR of the per-GPU partials)."""
+    (host XOR of the per-GPU partials).
 
-    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32):
+    With `points` (uint64, one per record) the handle is the sparse kind
+    (dpf_pir_db_create_sparse, keyword PIR): record j lives at domain point
+    points[j] instead of at index j, points may repeat (such records are
+    selected together), shards are record ranges over any number of GPUs, and
+    update()/read() take a record's position in the list.  The points are
+    fixed at creation."""
+
+    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
         if rec_bytes <= 0 or d.size % rec_bytes:
             raise ValueError("DB size must be a multiple of %d bytes" % rec_bytes)
@@ -765,7 +820,13 @@ class PirDB:
         self.rec_bytes = rec_bytes
         nrec = d.size // rec_bytes
         h = _vp()
-        if rec_bytes == 32:
+        if points is not None:
+            pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1)
+            if pts.size != nrec:
+                raise ValueError("points must hold one uint64 per record")
+            _check(lib().dpf_pir_db_create_sparse(pts.ctypes.data_as(_u64p), _buf(d), nrec, rec_bytes, logN, ngpus,
+                                                  ctypes.byref(h)))
+        elif rec_bytes == 32:
             _check(lib().dpf_pir_db_create(_buf(d), nrec, logN, ngpus, ctypes.byref(h)))
         elif rec_bytes % 32 == 0:
             _check(lib().dpf_pir_db_create_wide(_buf(d), nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))

@@ -146,6 +146,39 @@ uint32_t dpf_eval_frontier_level(uint32_t logN, size_t pts_per_key);
 int dpf_eval_batch_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, const uint64_t* d_xs,
                        size_t pts_per_key, uint32_t logN, uint8_t* d_out, void* d_work, size_t work_bytes,
                        void* stream);
+/* Eval of every key at ONE list of points, the answers as packed selection
+ * bits: d_xs [npts] is shared by all nkeys keys (unsorted, repeated and
+ * bit-63 points are fine; no per-key copy is made), and bit j%8 of byte j/8 of
+ * row k of d_bits [nkeys][bits_stride] is Eval(key_k, d_xs[j], logN): the bit
+ * dpf_eval_batch_dev returns for (key_k, d_xs[j]), for every logN it accepts,
+ * in EvalFull's bit order.  The kernel writes the first
+ * dpf_eval_bits_stride(npts) = 16*ceil(npts/128) bytes of every row, with
+ * zeros at bit positions >= npts of that span, and touches no byte of a row
+ * past it.  So the rows are valid d_bits input, with nrec = npts, of
+ * dpf_xor_fold_dev, dpf_xor_fold_sliced_any_dev, dpf_xor_scatter_dev and
+ * dpf_xor_scatter_sliced_any_dev: PIR over records that sit at arbitrary
+ * points of a large domain (keyword PIR) instead of a dense prefix of a
+ * subtree.  A wave evaluates 128 consecutive points of one key and turns its
+ * answers into the row's 16 bytes by wave ballots: 1/8 byte of output per
+ * query, no byte-per-query intermediate, no atomics.
+ * dpf_eval_bits_workspace_size is dpf_eval_workspace_size(nkeys, npts, logN):
+ * the expanded keys and the frontier, nothing that grows as nkeys*npts.  With
+ * that many work_bytes the points share each key's top tree levels; with no
+ * more than the expanded keys (dpf_eval_workspace_size(nkeys, 1, logN)) every
+ * walk starts at the root, as for dpf_eval_batch_dev; the bits are identical.
+ * DPF_ERR_KEYLEN for a short key; DPF_ERR_PARAM, each checked before any
+ * device call, when bits_stride is not a multiple of 16 or is below
+ * dpf_eval_bits_stride(npts), d_xs is not 8-byte aligned, d_bits or d_work is
+ * not 16-byte aligned, a pointer is null while nkeys and npts are nonzero, or
+ * work_bytes does not hold the expanded keys (nkeys * (logN-7+2) * 32 bytes;
+ * dpf_workspace_size(nkeys, logN) always does, but outgrows any device at
+ * deep logN).  nkeys == 0 or npts == 0 returns DPF_OK without a launch.
+ * Asynchronous on `stream`. */
+size_t dpf_eval_bits_stride(size_t npts);
+size_t dpf_eval_bits_workspace_size(size_t nkeys, size_t npts, uint32_t logN);
+int dpf_eval_bits_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, const uint64_t* d_xs,
+                      size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
+                      void* stream);
 
 /* ---- Introspection: which form of a kernel a call runs -------------------
  * The tree kernel is one source but many kernels at run time; these say which
@@ -563,6 +596,55 @@ int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out);
  * dpf_pir_db_update.  Synchronous. */
 int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t key_len, size_t nkeys, const uint8_t* msgs);
 void dpf_pir_db_free(void* handle);
+
+/* ---- PIR over a sparse key set (keyword PIR) ----------------------------
+ * Record j of the DB lives at domain point d_points[j], any point of the
+ * 2^logN domain, instead of at position j of a subtree: the client hashes its
+ * keyword to a point, runs Gen(point, logN) and sends one key to each server.
+ * The selection bits come from dpf_eval_bits_dev at the records' points; the
+ * fold and the scatter are those of the dense entry points.
+ * Device forms: d_dbs is the any-width sliced layout of nrec records
+ * (rec_bytes a positive multiple of 4 up to DPF_PIR_MAX_REC_BYTES), d_points
+ * [nrec] uint64.  The answer for key k is the XOR of the records j with
+ * Eval(key_k, d_points[j]) = 1 (d_ans [nkeys][rec_bytes], overwritten; zeros
+ * for nrec == 0); the write is the dual, record j ^= XOR of d_msgs[k] over the
+ * same keys.  Points may repeat: such records are selected together.  Each is
+ * dpf_eval_bits_dev into a bit area inside d_work, then the fold
+ * (dpf_xor_fold_sliced_any_dev) or the scatter
+ * (dpf_xor_scatter_sliced_any_dev); DPF_PIR_FUSED has no part in either.
+ * d_work holds dpf_pir_sparse_workspace_size(nkeys, nrec, logN) bytes: the
+ * Eval-bits workspace, nkeys * dpf_eval_bits_stride(nrec) bytes of bit rows
+ * and dpf_xor_fold_workspace_size(), each rounded up to 16 bytes.  Checked
+ * before any device call, in this order: rec_bytes (DPF_ERR_PARAM), the key
+ * length (DPF_ERR_KEYLEN), then null and misaligned buffers (DPF_ERR_PARAM;
+ * d_dbs, d_msgs and d_work 16-byte, d_points 8-byte, d_ans 4-byte aligned;
+ * the answer form allows null buffers it has no work for, the write form
+ * none).  nkeys == 0, and for the write nrec == 0, return DPF_OK without a
+ * launch.  Asynchronous on `stream`. */
+size_t dpf_pir_sparse_workspace_size(size_t nkeys, uint64_t nrec, uint32_t logN);
+int dpf_pir_answer_sparse_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                              const uint64_t* d_points, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                              uint8_t* d_ans, void* d_work, void* stream);
+int dpf_pir_write_sparse_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                             const uint64_t* d_points, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec,
+                             size_t rec_bytes, void* d_work, void* stream);
+/* A resident DB of the sparse kind: points [nrec] and db [nrec][rec_bytes]
+ * (tightly packed, every width 1 .. DPF_PIR_MAX_REC_BYTES, padded to a
+ * multiple of 4 on the device as dpf_pir_db_create_any does).  logN <= 63,
+ * and a point >= 2^logN is DPF_ERR_PARAM (*handle = NULL).  Repeated points
+ * are allowed: both records are selected together, so a client reads their
+ * XOR.  ngpus is any count up to the opened devices (<= 0: all of them):
+ * shard g holds the ceil(ceil(nrec/256) / ngpus) * 256 records starting at g
+ * times that many, a range of whole super-groups and not a subtree, with its
+ * slice of the points beside it in HBM.  The points are fixed at creation.
+ * dpf_pir_answer and dpf_pir_db_write on the handle run the sparse device
+ * forms per shard and XOR the partial answers on the host;
+ * dpf_pir_db_update, dpf_pir_db_read, dpf_pir_db_nrec and
+ * dpf_pir_db_rec_bytes keep their contracts, idx being a record's position
+ * in the list.  With env DPF_PIR_FOLD=lds (row-major shards) creation is
+ * DPF_ERR_PARAM. */
+int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t nrec, size_t rec_bytes,
+                             uint32_t logN, int ngpus, void** handle);
 
 #ifdef __cplusplus
 }
