@@ -1,0 +1,342 @@
+// capi_pir_db.hip — the resident PIR database of the C ABI (include/dpf_hip.h):
+// a handle that keeps a DB sharded over the opened devices and answers,
+// updates, reads and privately writes it from host buffers.  Every shard runs
+// the device-resident forms of capi_pir.hip on its device's stream under the
+// device's mutex; pir_update_plan.hpp has the shards' record ranges and the
+// planners of update / read that must agree with them.  No kernel is defined here.
+#include <stdlib.h>
+#include <string.h>
+
+#include "capi_common.hpp"
+#include "pir_update_plan.hpp"
+
+using namespace dpfc;
+using dpfh::kStageBytes;
+
+namespace {
+
+// A PIR handle owns references to the devices its shards live on, so it
+// stays usable (and freeable) after dpf_gpu_shutdown.
+struct PirDb {
+    uint32_t logN = 0, pbits = 0;
+    uint64_t nrec = 0;
+    size_t rec_bytes = 32;         // the caller's record width
+    size_t w4 = 32;                // bytes per record on the device: rec_bytes rounded up to a multiple of 4, pad zero
+    bool sliced = true;            // shards in the bit-sliced layout (the matrix-core fold)
+    // Shard g holds the records ranges.lo(g) .. ranges.hi(g) -- dense: the
+    // slice of subtree (pbits, g); sparse (dpf_pir_db_create_sparse: record j
+    // lives at domain point points[j]): a range of whole super-groups and not
+    // a subtree (pbits = 0), with its slice of the points beside it in HBM.
+    bool sparse = false;
+    dpfh::ShardRanges ranges;
+    DevList devs;                  // per shard: its device
+    std::vector<void*> shard;      // per device: its DB slice
+    std::vector<uint64_t> shard_n; // records in that slice
+    std::vector<void*> shard_pts;  // per device: uint64 points of its records (sparse)
+    ~PirDb() {
+        for (size_t i = 0; i < shard.size(); ++i) {
+            DeviceGuard gd(devs[i]->id);
+            (void)hipFree(shard[i]);
+            if (i < shard_pts.size()) (void)hipFree(shard_pts[i]);
+        }
+    }
+};
+
+// Upload chunk of a sliced shard: whole super-groups, at most this many bytes.
+constexpr uint64_t kPirUploadChunk = 256ull << 20;
+
+// Rows of `w` bytes between a tight host array [n][w] and device rows of
+// `pitch` >= w bytes (the handle's padded records), in either direction.
+hipError_t copy_rows_up(void* dev, size_t pitch, const uint8_t* host, size_t w, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (w == pitch) return hipMemcpyAsync(dev, host, n * w, hipMemcpyHostToDevice, st);
+    if (hipError_t e = hipMemsetAsync(dev, 0, n * pitch, st); e != hipSuccess) return e;   // the pad bytes are zero
+    return hipMemcpy2DAsync(dev, pitch, host, w, w, n, hipMemcpyHostToDevice, st);
+}
+hipError_t copy_rows_down(uint8_t* host, const void* dev, size_t pitch, size_t w, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (w == pitch) return hipMemcpyAsync(host, dev, n * w, hipMemcpyDeviceToHost, st);
+    return hipMemcpy2DAsync(host, w, dev, pitch, w, n, hipMemcpyDeviceToHost, st);
+}
+
+// DPF_PIR_FOLD=lds keeps the row-major shards and the LDS fold (A/B runs).
+bool lds_shards() {
+    static const bool lds = [] {
+        const char* e = getenv("DPF_PIR_FOLD");
+        return e && e[0] == 'l';
+    }();
+    return lds;
+}
+
+// Shard g of a handle under construction, on its device: the allocation(s),
+// the points, and the records [lo, hi) of db.  The handle owns each buffer
+// from the moment it exists, so ~PirDb frees a half-built handle.
+int upload_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t g, const uint8_t* db, const uint64_t* points) {
+    const uint64_t lo = h->ranges.lo(g), hi = h->ranges.hi(g);
+    const size_t rec_bytes = h->w4, caller_bytes = h->rec_bytes;
+    DeviceGuard gd(dev->id);
+    void* p = nullptr;
+    const size_t bytes = h->sliced ? dpf_pir_db_sliced_size_any(hi - lo, rec_bytes)
+                                   : std::max<uint64_t>(hi - lo, 1) * rec_bytes;
+    if (hipMalloc(&p, bytes) != hipSuccess) return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
+    h->devs.push_back(dev);
+    h->shard.push_back(p);
+    h->shard_n.push_back(hi - lo);
+    if (h->sparse) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<uint64_t>(hi - lo, 2) * 8) != hipSuccess)
+            return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
+        h->shard_pts.push_back(q);
+        if (hi > lo && hipMemcpy(q, points + lo, (hi - lo) * 8, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(DPF_ERR_HIP, "dpf: DB upload failed");
+    }
+    if (hi <= lo) return DPF_OK;
+    if (!h->sliced) {
+        if (hipMemcpy(p, db + lo * rec_bytes, (hi - lo) * rec_bytes, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(DPF_ERR_HIP, "dpf: DB upload failed");
+        return DPF_OK;
+    }
+    // Row-major records up through a bounded staging buffer, in chunks of
+    // whole super-groups, each sliced into its place in the shard (a
+    // chunk that starts at a multiple of 256 records is a contiguous
+    // sub-range of the sliced layout).
+    const uint64_t chunk = std::max<uint64_t>(256, kPirUploadChunk / rec_bytes / 256 * 256);
+    void* tmp = nullptr;
+    if (hipMalloc(&tmp, std::min<uint64_t>(hi - lo, chunk) * rec_bytes) != hipSuccess)
+        return fail(DPF_ERR_NOMEM, "dpf: DB staging allocation failed");
+    bool ok = true;
+    for (uint64_t r0 = lo; ok && r0 < hi; r0 += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, hi - r0);
+        ok = copy_rows_up(tmp, rec_bytes, db + r0 * caller_bytes, caller_bytes, n, nullptr) == hipSuccess &&
+             dpfk::launch_slice_db((const uint8_t*)tmp, n, rec_bytes, (uint8_t*)p + (r0 - lo) * rec_bytes, nullptr) ==
+                 hipSuccess &&
+             hipDeviceSynchronize() == hipSuccess;   // tmp is reused by the next chunk
+    }
+    (void)hipFree(tmp);
+    return ok ? DPF_OK : fail(DPF_ERR_HIP, "dpf: DB upload failed");
+}
+
+// rule: RecRule::Mul32 (dpf_pir_db_create, _wide) or Bytes1 (_any and _sparse:
+// every width from 1 byte, shards at w4 bytes per record).  points: the
+// sparse kind (any device count; each shard with its points beside it).
+int pir_db_create(RecRule rule, const uint64_t* points, bool sparse, const uint8_t* db, uint64_t nrec, size_t caller_bytes,
+                  uint32_t logN, int ngpus, void** handle) {
+    // What needs no device.
+    if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
+    *handle = nullptr;
+    if (int rc = check_rec_bytes(rule, caller_bytes)) return rc;
+    if (logN > 63 || (!sparse && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: DB larger than 2^logN");
+    if (sparse) {
+        if (nrec > 0 && (!points || !db)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+        for (uint64_t j = 0; j < nrec; ++j)
+            if ((points[j] >> logN) != 0) return fail(DPF_ERR_PARAM, "dpf: point outside the 2^logN domain");
+    }
+    // The devices and the shards' ranges.
+    int have = 0;
+    const DevList devs = pick_devs(0, &have);
+    if (have <= 0) return have;
+    const int want = ngpus <= 0 ? have : ngpus;
+    uint32_t pb = 0;
+    if (sparse) {
+        if (want > have) return fail(DPF_ERR_PARAM, "dpf: ngpus must be <= opened devices");
+    } else if (want > have || !dpfh::gpus_to_pb(want, stop_of(logN), &pb)) {
+        return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= opened devices and 2^(logN-7)");
+    }
+    auto h = std::make_unique<PirDb>();
+    h->logN = logN;
+    h->pbits = pb;
+    h->nrec = nrec;
+    h->rec_bytes = caller_bytes;
+    h->w4 = (caller_bytes + 3) & ~(size_t)3;
+    h->sliced = !lds_shards();
+    if (!h->sliced && !rec_bytes_ok(RecRule::Mul32Uncapped, caller_bytes))
+        return fail(DPF_ERR_PARAM, "dpf: row-major shards (DPF_PIR_FOLD=lds) take multiples of 32 bytes only");
+    if (!h->sliced && sparse)
+        return fail(DPF_ERR_PARAM, "dpf: sparse handles keep sliced shards only (DPF_PIR_FOLD=lds set)");
+    h->sparse = sparse;
+    h->ranges = sparse ? dpfh::sparse_shards(nrec, (size_t)want) : dpfh::dense_shards(nrec, logN, pb);
+    // The uploads.
+    for (int g = 0; g < want; ++g)
+        if (int rc = upload_shard(h.get(), devs[(size_t)g], (size_t)g, db, points)) return rc;
+    *handle = h.release();
+    return DPF_OK;
+}
+
+// One shard's turn in dpf_pir_answer / dpf_pir_db_write: under its device's
+// mutex and on its device, staging of at least keys_bytes / out_bytes and the
+// workspace of the shard's device form, the keys up, then body(d) and the
+// stream drained, so a concurrent call sees the shard before or after.
+template <class Body>
+int on_shard(PirDb* h, size_t s, const uint8_t* keys, size_t klen, size_t nkeys, size_t keys_bytes, size_t out_bytes,
+             Body body) {
+    Dev& d = *h->devs[s];
+    std::lock_guard<std::mutex> lk(d.mu);
+    DeviceGuard gd(d.id);
+    HIP_TRY(d.keys.ensure(keys_bytes));
+    HIP_TRY(d.work.ensure(h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
+                                    : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+    HIP_TRY(d.out.ensure(out_bytes));
+    HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
+    if (int rc = body(d)) return rc;
+    HIP_TRY(hipStreamSynchronize(d.st));
+    return DPF_OK;
+}
+
+// The device form of shard s by its kind (sparse, sliced, row-major; the last
+// takes multiples of 32 bytes, the others any multiple of 4): the answers
+// into, or with `write` the messages from, d.out.
+int shard_dev(PirDb* h, size_t s, Dev& d, size_t klen, size_t nkeys, bool write) {
+    const uint8_t* k = (const uint8_t*)d.keys.p;
+    uint8_t *db = (uint8_t*)h->shard[s], *io = (uint8_t*)d.out.p;
+    const uint64_t n = h->shard_n[s];
+    if (h->sparse) {
+        const uint64_t* pts = (const uint64_t*)h->shard_pts[s];
+        return write ? dpf_pir_write_sparse_dev(d.id, k, klen, nkeys, h->logN, pts, io, db, n, h->w4, d.work.p, d.st)
+                     : dpf_pir_answer_sparse_dev(d.id, k, klen, nkeys, h->logN, pts, db, n, h->w4, io, d.work.p, d.st);
+    }
+    if (write)
+        return (h->sliced ? dpf_pir_write_sliced_any_dev : dpf_pir_write_wide_dev)(
+            d.id, k, klen, nkeys, h->logN, h->pbits, s, io, db, n, h->w4, d.work.p, d.st);
+    return (h->sliced ? dpf_pir_answer_sliced_any_dev : dpf_pir_answer_wide_dev)(
+        d.id, k, klen, nkeys, h->logN, h->pbits, s, db, n, h->w4, io, d.work.p, d.st);
+}
+
+// One chunk of a shard's planned entries [a, b): the local indices and (for
+// an update) the records go up through the device's staging buffers, the
+// device form runs on the device's stream under its mutex, and the call
+// returns when the stream is idle: a concurrent dpf_pir_answer sees the shard
+// before or after the chunk, never in between.
+int pir_update_chunk(PirDb* h, size_t s, const dpfh::PirUpdatePlan& plan, size_t a, size_t b, const uint8_t* recs,
+                     uint8_t* out, std::vector<uint8_t>& host) {
+    const size_t rb = h->rec_bytes, w4 = h->w4, m = b - a;
+    Dev& d = *h->devs[s];
+    uint8_t* db = (uint8_t*)h->shard[s];
+    const uint64_t nrec = h->shard_n[s];
+    // Entries that are consecutive in the caller's arrays (sorted input) go
+    // up / come back straight from / to them; otherwise through `host`.
+    bool direct = true;
+    for (size_t k = 1; direct && k < m; ++k) direct = plan.src[a + k] == plan.src[a] + k;
+    uint8_t* stage = nullptr;
+    if (direct) {
+        stage = recs ? const_cast<uint8_t*>(recs) + plan.src[a] * rb : out + plan.src[a] * rb;
+    } else {
+        host.resize(m * rb);
+        stage = host.data();
+        if (recs)
+            for (size_t k = 0; k < m; ++k) memcpy(stage + k * rb, recs + plan.src[a + k] * rb, rb);
+    }
+    std::lock_guard<std::mutex> lk(d.mu);
+    DeviceGuard gd(d.id);
+    HIP_TRY(d.xs.ensure(m * 8));
+    HIP_TRY(d.out.ensure(m * w4));
+    const uint64_t* d_idx = (const uint64_t*)d.xs.p;
+    HIP_TRY(hipMemcpyAsync(d.xs.p, plan.local.data() + a, m * 8, hipMemcpyHostToDevice, d.st));
+    if (recs) {
+        HIP_TRY(copy_rows_up(d.out.p, w4, stage, rb, m, d.st));
+        HIP_TRY((h->sliced ? dpfk::launch_update_sliced : dpfk::launch_update_rows)(db, nrec, w4, d_idx,
+                                                                                    (const uint8_t*)d.out.p, m, d.st));
+    } else {
+        HIP_TRY((h->sliced ? dpfk::launch_gather_sliced : dpfk::launch_gather_rows)(db, nrec, w4, d_idx, m,
+                                                                                    (uint8_t*)d.out.p, d.st));
+        HIP_TRY(copy_rows_down(stage, d.out.p, w4, rb, m, d.st));
+    }
+    HIP_TRY(hipStreamSynchronize(d.st));
+    if (d.out.cap > 2 * kStageBytes) d.out.release();   // a large chunk's staging is not kept
+    if (d.xs.cap > kStageBytes) d.xs.release();
+    if (out && !direct)
+        for (size_t k = 0; k < m; ++k) memcpy(out + plan.src[a + k] * rb, stage + k * rb, rb);
+    return DPF_OK;
+}
+
+// dpf_pir_db_update (recs) and dpf_pir_db_read (out): plan on the host, then
+// shard by shard in chunks of at most kPirUploadChunk bytes of records.
+int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const uint8_t* recs, uint8_t* out) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (n == 0) return DPF_OK;
+    if (!idx || (!recs && !out)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    dpfh::PirUpdatePlan plan;
+    if (!(h->sparse ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->ranges.slice, h->shard.size(), recs != nullptr, &plan)
+                    : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
+        return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
+    const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->w4);
+    std::vector<uint8_t> host;
+    for (size_t s = 0; s + 1 < plan.shard_off.size(); ++s)
+        for (size_t a = plan.shard_off[s]; a < plan.shard_off[s + 1]; a += chunk)
+            if (int rc = pir_update_chunk(h, s, plan, a, std::min(a + chunk, plan.shard_off[s + 1]), recs, out, host))
+                return rc;
+    return DPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus, void** handle) {
+    return pir_db_create(RecRule::Mul32, nullptr, false, db, nrec, 32, logN, ngpus, handle);
+}
+int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
+                           void** handle) {
+    return pir_db_create(RecRule::Mul32, nullptr, false, db, nrec, rec_bytes, logN, ngpus, handle);
+}
+int dpf_pir_db_create_any(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle) {
+    return pir_db_create(RecRule::Bytes1, nullptr, false, db, nrec, rec_bytes, logN, ngpus, handle);
+}
+int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN,
+                             int ngpus, void** handle) {
+    return pir_db_create(RecRule::Bytes1, points, true, db, nrec, rec_bytes, logN, ngpus, handle);
+}
+
+size_t dpf_pir_db_rec_bytes(void* handle) { return handle ? ((PirDb*)handle)->rec_bytes : 0; }
+uint64_t dpf_pir_db_nrec(void* handle) { return handle ? ((PirDb*)handle)->nrec : 0; }
+void dpf_pir_db_free(void* handle) { delete (PirDb*)handle; }
+
+int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, uint8_t* ans) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (int rc = check_key(klen, h->logN)) return rc;
+    const int g = (int)h->shard.size();
+    const size_t rb = h->rec_bytes, w4 = h->w4;
+    std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * rb));
+    int rc = shard((size_t)g, g, [&](int, size_t s, size_t) {
+        return on_shard(h, s, keys, klen, nkeys, std::max<size_t>(1, nkeys * klen), std::max<size_t>(32, nkeys * w4),
+                        [&](Dev& d) {
+                            if (int r = shard_dev(h, s, d, klen, nkeys, false)) return r;
+                            HIP_TRY(copy_rows_down(part[s].data(), d.out.p, w4, rb, nkeys, d.st));
+                            return (int)DPF_OK;
+                        });
+    });
+    if (rc) return rc;
+    memset(ans, 0, nkeys * rb);
+    for (int i = 0; i < g; ++i)
+        for (size_t b = 0; b < nkeys * rb; ++b) ans[b] ^= part[(size_t)i][b];
+    return DPF_OK;
+}
+
+int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, size_t n) {
+    return pir_update_or_read(handle, idx, n, recs, nullptr);
+}
+int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out) {
+    return pir_update_or_read(handle, idx, n, nullptr, out);
+}
+
+// Every shard applies the batch to its slice: keys and messages up through
+// the device's staging buffers, tree and scatter on the device's stream.
+int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, const uint8_t* msgs) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (int rc = check_key(klen, h->logN)) return rc;
+    if (nkeys == 0) return DPF_OK;
+    if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    const int g = (int)h->shard.size();
+    const size_t rb = h->rec_bytes, w4 = h->w4;
+    return shard((size_t)g, g, [&](int, size_t s, size_t) {
+        if (h->shard_n[s] == 0) return (int)DPF_OK;
+        return on_shard(h, s, keys, klen, nkeys, nkeys * klen, nkeys * w4, [&](Dev& d) {
+            HIP_TRY(copy_rows_up(d.out.p, w4, msgs, rb, nkeys, d.st));   // zero pad bytes: the DB's stay zero
+            return shard_dev(h, s, d, klen, nkeys, true);
+        });
+    });
+}
+
+}  // extern "C"

@@ -24,6 +24,26 @@ struct PirUpdatePlan {
     std::vector<size_t> shard_off;
 };
 
+// Which of a handle's nrec records its shards hold: shard g has [lo(g), hi(g)),
+// consecutive ranges of `slice` records cut off at nrec.  The handle uploads
+// by these ranges and the planners below split by the same slice, so local
+// index l of shard g is record lo(g) + l (tests/c/pir_update_plan_test.cpp).
+struct ShardRanges {
+    uint64_t nrec = 0, slice = 0;
+    uint64_t lo(size_t g) const { return std::min<uint64_t>(nrec, (uint64_t)g * slice); }
+    uint64_t hi(size_t g) const { return std::min<uint64_t>(nrec, lo(g) + slice); }
+};
+// Dense: shard g is the DB's part under subtree (pbits, g), 2^(logN - pbits)
+// records (plan_pir_update).
+inline ShardRanges dense_shards(uint64_t nrec, uint32_t logN, uint32_t pbits) {
+    return ShardRanges{nrec, 1ull << (logN - pbits)};
+}
+// Sparse: an even split in whole super-groups of 256 records, so that every
+// shard's sliced layout starts on one (plan_pir_update_ranges with cap = slice).
+inline ShardRanges sparse_shards(uint64_t nrec, size_t nshards) {
+    return ShardRanges{nrec, ((nrec + 255) / 256 + (uint64_t)nshards - 1) / (uint64_t)nshards * 256};
+}
+
 // The planner behind both shardings below: split(v, &shard, &local) places
 // index v (shards ascending with v), nshards of them.
 template <class Split>

@@ -144,6 +144,42 @@ int main() {
         CHECK(plan_pir_update(srt.data(), n, nrec, 40, 2, false, &p));
         for (size_t k = 0; k < n; ++k) CHECK(p.src[k] == k);
     }
+    // The shards' record ranges (what the handle uploads) against the planners
+    // (where an update lands): the ranges tile [0, nrec) in order, sparse ones
+    // start on whole super-groups, and every index the planner places in
+    // shard s at local l is record lo(s) + l of a shard that holds it.
+    {
+        const uint64_t nrecs[] = {0, 1, 255, 256, 257, 1000, (1ull << 20) + 1};
+        const uint32_t logN = 21;
+        auto check = [](const dpfh::ShardRanges& r, size_t nshards, bool sparse, uint32_t pbits) {
+            uint64_t at = 0;
+            for (size_t g = 0; g < nshards; ++g) {
+                CHECK(r.lo(g) == at && r.hi(g) >= r.lo(g) && r.hi(g) <= r.nrec);
+                if (sparse) CHECK(r.lo(g) % 256 == 0 || r.lo(g) == r.nrec);
+                at = r.hi(g);
+            }
+            CHECK(at == r.nrec);
+            // Both edges of every shard, and a stride through the records, out of order.
+            std::vector<uint64_t> idx;
+            for (size_t g = 0; g < nshards; ++g)
+                if (r.hi(g) > r.lo(g)) idx.push_back(r.hi(g) - 1), idx.push_back(r.lo(g));
+            for (uint64_t v = 0; v < r.nrec; v += r.nrec / 61 + 1) idx.push_back(r.nrec - 1 - v);
+            PirUpdatePlan p;
+            CHECK(sparse ? dpfh::plan_pir_update_ranges(idx.data(), idx.size(), r.nrec, r.slice, nshards, false, &p)
+                         : plan_pir_update(idx.data(), idx.size(), r.nrec, logN, pbits, false, &p));
+            CHECK(p.shard_off.size() == nshards + 1 && p.shard_off[nshards] == idx.size());
+            for (size_t s = 0; s < nshards; ++s)
+                for (size_t k = p.shard_off[s]; k < p.shard_off[s + 1]; ++k)
+                    CHECK(r.lo(s) + p.local[k] == idx[p.src[k]] && idx[p.src[k]] < r.hi(s));
+        };
+        for (uint64_t nrec : nrecs) {
+            for (uint32_t pbits : {0u, 1u, 3u}) check(dpfh::dense_shards(nrec, logN, pbits), (size_t)1 << pbits, false, pbits);
+            for (size_t nshards : {1, 2, 3, 8}) check(dpfh::sparse_shards(nrec, nshards), nshards, true, 0);
+        }
+        // The sparse split is even in whole super-groups: 1000 records over 3 -> 512, 488, 0.
+        const dpfh::ShardRanges r = dpfh::sparse_shards(1000, 3);
+        CHECK(r.slice == 512 && r.hi(0) == 512 && r.lo(1) == 512 && r.hi(1) == 1000 && r.lo(2) == 1000 && r.hi(2) == 1000);
+    }
     printf("pir_update_plan ok\n");
     return 0;
 }

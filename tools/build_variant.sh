@@ -12,7 +12,7 @@ mkdir -p "$O"
 make -s -C "$REPO/dpf-go_amd" > /dev/null
 HIPCC=/opt/rocm/bin/hipcc
 CXX=(-O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=gfx950)
-HIP=(dpf_kernels bs_kernels pir_kernels pir_fold_rows pir_fold_sliced pir_db_ops dpf_capi)
+HIP=(dpf_kernels bs_kernels pir_kernels pir_fold_rows pir_fold_sliced pir_db_ops dpf_capi capi_pir capi_pir_db)
 for f in "${HIP[@]}"; do
   X=""; [ "$f" = dpf_kernels ] && X="$KFLAGS"
   # shellcheck disable=SC2086
