@@ -2,7 +2,8 @@
 //   dpf_capi.hip     the device registry and the knobs, the staging pipeline,
 //                    the tree, Eval and Eval-bits entries, the form queries
 //   capi_pir.hip     every device-resident PIR form (slice, fold, scatter,
-//                    answer, write, update / gather, the sparse composites)
+//                    answer, write, update / gather, the sparse composites,
+//                    the grouped forms)
 //   capi_pir_db.hip  the resident-DB handle (create, answer, update / read, write)
 // Here: the error slot, the device objects, and one definition of each
 // workspace layout and of each argument rule.  An entry point is a short list
@@ -26,6 +27,7 @@
 #include "bs_kernels.hpp"
 #include "dpf_kernels.hpp"
 #include "eval_bits_plan.hpp"
+#include "pir_group_plan.hpp"
 #include "pir_kernels.hpp"
 #include "stage_plan.hpp"
 
@@ -214,6 +216,28 @@ inline SparseWs sparse_ws(void* d_work, size_t nkeys, uint64_t nrec, uint32_t lo
     return w;
 }
 
+// d_work of the grouped PIR composite: [tree workspace of all ngroups * kpg
+// keys | selection bits, a whole-domain EvalFull row of per_key bytes a key |
+// the grouped fold's scratch], the first two parts padded to 256 B.  The
+// grouped fold writes no scratch (dpfh::GroupedFoldPlan::scratch_bytes); its
+// size function keeps the ABI's 16-byte minimum.
+inline size_t group_fold_ws_bytes() { return std::max<size_t>(16, dpfh::GroupedFoldPlan{}.scratch_bytes()); }
+struct GroupWs {
+    uint8_t* bits;
+    uint64_t per_key;
+    uint32_t* scratch;
+    size_t total;
+};
+inline GroupWs group_ws(void* d_work, size_t nkeys, uint32_t stop) {
+    GroupWs w;
+    w.per_key = (uint64_t)16 << stop;
+    const size_t tree = align256(tree_ws_bytes(nkeys, stop, 0, nkeys)), bits = align256(nkeys * w.per_key);
+    w.bits = at(d_work, tree);
+    w.scratch = (uint32_t*)at(d_work, tree + bits);
+    w.total = tree + bits + group_fold_ws_bytes();
+    return w;
+}
+
 // ---- expanded keys in a caller's d_work (dpf_capi.hip) -----------------------
 // Every entry point that expands keys into a caller's d_work records what it
 // left there (the tree_ws layout), so a later dpf_evalfull_expanded_dev never
@@ -289,6 +313,13 @@ inline int check_subtree(size_t klen, uint32_t logN, uint32_t prefix_bits, uint6
 inline int check_sel_bits(size_t bits_stride, uint64_t nrec) {
     if (bits_stride % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16");
     if (nrec > (uint64_t)bits_stride * 8) return fail(DPF_ERR_PARAM, "dpf: more records than selection bits per key");
+    return DPF_OK;
+}
+
+// A grouped call's key rows: ngroups * keys_per_group of them, counted in 32 bits.
+inline int check_group_keys(uint64_t ngroups, uint64_t keys_per_group) {
+    if (ngroups != 0 && keys_per_group > (uint64_t)UINT32_MAX / ngroups)
+        return fail(DPF_ERR_PARAM, "dpf: ngroups * keys_per_group does not fit 32 bits");
     return DPF_OK;
 }
 

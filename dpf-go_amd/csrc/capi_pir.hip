@@ -379,4 +379,87 @@ int dpf_pir_write_sparse_dev(int device, const uint8_t* d_keys, size_t klen, siz
     return DPF_OK;
 }
 
+// ---- grouped PIR: ngroups small DBs of one shape, each with its own keys ----
+// The layout is the any-width sliced layout of one flat DB (pir_group_plan.hpp);
+// the fold has a group coordinate (launch_pir_fold_grouped).
+uint64_t dpf_pir_group_stride(uint64_t nrec) { return dpfh::group_stride(nrec); }
+
+size_t dpf_pir_db_grouped_size(uint64_t ngroups, uint64_t nrec, size_t rec_bytes) {
+    uint64_t bytes = 0;
+    if (!rec_bytes_ok(RecRule::Mul4, rec_bytes) || !dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return 0;
+    return std::max<size_t>(16, bytes);
+}
+
+int dpf_pir_db_slice_grouped_dev(int device, const uint8_t* d_db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes,
+                                 uint8_t* d_dbs, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    uint64_t bytes = 0;
+    if (!dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
+    if (bytes > 0 && !present(d_db, d_dbs)) return null_buffer();
+    if (!aligned(16, d_db, d_dbs)) return misaligned_buffer();
+    if (bytes == 0) return DPF_OK;
+    DeviceGuard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t gs = dpfh::group_stride(nrec);
+    if (gs == nrec) {   // no padding: the row-major DB is the flat one
+        HIP_TRY(dpfk::launch_slice_db(d_db, ngroups * nrec, rec_bytes, d_dbs, st));
+        return DPF_OK;
+    }
+    for (uint64_t i = 0; i < ngroups; ++i)   // a group's last super-group is zero-filled behind its nrec records
+        HIP_TRY(dpfk::launch_slice_db(d_db + i * nrec * rec_bytes, nrec, rec_bytes, d_dbs + i * gs * rec_bytes, st));
+    return DPF_OK;
+}
+
+size_t dpf_xor_fold_grouped_workspace_size(uint64_t ngroups, uint64_t keys_per_group, size_t rec_bytes) {
+    if (!rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK) return 0;
+    return group_fold_ws_bytes();
+}
+
+int dpf_xor_fold_grouped_dev(int device, const uint8_t* d_bits, size_t bits_stride, uint64_t ngroups,
+                             uint64_t keys_per_group, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                             uint8_t* d_ans, void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_sel_bits(bits_stride, nrec)) return rc;
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    const uint64_t nkeys = ngroups * keys_per_group;
+    if (nkeys > 0 && !(present(d_ans, d_work) && (nrec == 0 || present(d_bits, d_dbs)))) return null_buffer();
+    if (!aligned(16, d_bits, d_dbs, d_work) || !aligned(4, d_ans)) return misaligned_buffer();
+    if (nkeys == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(dpfk::launch_pir_fold_grouped((const uint32_t*)d_bits, bits_stride / 4, d_dbs, ngroups,
+                                          (uint32_t)keys_per_group, nrec, rec_bytes, (uint32_t*)d_ans, (uint32_t*)d_work,
+                                          (hipStream_t)stream));
+    return DPF_OK;
+}
+
+size_t dpf_pir_grouped_workspace_size(uint64_t ngroups, uint64_t keys_per_group, uint32_t logN, size_t rec_bytes) {
+    if (!rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK) return 0;
+    return group_ws(nullptr, ngroups * keys_per_group, stop_of(logN)).total;
+}
+
+int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t klen, uint64_t ngroups, uint64_t keys_per_group,
+                               uint32_t logN, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans,
+                               void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_subtree(klen, logN, 0, 0, nrec)) return rc;   // the key, then nrec <= 2^logN
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    const size_t nkeys = ngroups * keys_per_group;
+    if (int rc = check_answer_bufs(d_keys, nkeys, d_dbs, nrec, d_ans, d_work)) return rc;
+    if (nkeys == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (nrec == 0) {
+        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        return DPF_OK;
+    }
+    const uint32_t stop = stop_of(logN);
+    const GroupWs w = group_ws(d_work, nkeys, stop);
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, 0, 0, w.bits, w.per_key, d_work, st, want_bs()));
+    HIP_TRY(dpfk::launch_pir_fold_grouped((const uint32_t*)w.bits, w.per_key / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
+                                          nrec, rec_bytes, (uint32_t*)d_ans, w.scratch, st));
+    return DPF_OK;
+}
+
 }  // extern "C"

@@ -28,6 +28,14 @@ struct PirDb {
     // lives at domain point points[j]): a range of whole super-groups and not
     // a subtree (pbits = 0), with its slice of the points beside it in HBM.
     bool sparse = false;
+    // Grouped (dpf_pir_db_create_grouped): ngroups
+    // groups of gnrec records, nrec = ngroups * gnrec the caller's index space.
+    // Shard s holds the whole groups [group_lo(s), group_hi(s)), gps of them,
+    // and `ranges` is in flat positions of the grouped layout (pir_group_plan.hpp).
+    bool grouped = false;
+    uint64_t ngroups = 0, gnrec = 0, gps = 0;
+    uint64_t group_lo(size_t s) const { return std::min<uint64_t>(ngroups, (uint64_t)s * gps); }
+    uint64_t group_hi(size_t s) const { return std::min<uint64_t>(ngroups, group_lo(s) + gps); }
     dpfh::ShardRanges ranges;
     DevList devs;                  // per shard: its device
     std::vector<void*> shard;      // per device: its DB slice
@@ -116,6 +124,75 @@ int upload_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t g, const uint
     return ok ? DPF_OK : fail(DPF_ERR_HIP, "dpf: DB upload failed");
 }
 
+// Shard s of a grouped handle under construction: its groups of db
+// [ngroups][gnrec][rec_bytes] go up through a staging buffer of whole groups
+// (at least one, however large) laid out as the flat DB, zero records behind
+// each group's gnrec, and are sliced into their place in the shard.
+int upload_grouped_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t s, const uint8_t* db) {
+    const uint64_t g0 = h->group_lo(s), g1 = h->group_hi(s), n = h->gnrec, gs = dpfh::group_stride(n);
+    const size_t w4 = h->w4, rb = h->rec_bytes;
+    DeviceGuard gd(dev->id);
+    void* p = nullptr;
+    if (hipMalloc(&p, dpf_pir_db_grouped_size(g1 - g0, n, w4)) != hipSuccess)
+        return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
+    h->devs.push_back(dev);
+    h->shard.push_back(p);
+    h->shard_n.push_back((g1 - g0) * gs);
+    if (g1 <= g0 || n == 0) return DPF_OK;
+    const uint64_t per = std::max<uint64_t>(1, kPirUploadChunk / (gs * w4));   // groups per staging chunk
+    uint8_t* tmp = nullptr;
+    if (hipMalloc((void**)&tmp, std::min<uint64_t>(per, g1 - g0) * gs * w4) != hipSuccess)
+        return fail(DPF_ERR_NOMEM, "dpf: DB staging allocation failed");
+    bool ok = true;
+    for (uint64_t g = g0; ok && g < g1; g += per) {
+        const uint64_t m = std::min<uint64_t>(per, g1 - g);
+        if (gs == n) {
+            ok = copy_rows_up(tmp, w4, db + g * n * rb, rb, m * n, nullptr) == hipSuccess;
+        } else {
+            ok = hipMemsetAsync(tmp, 0, m * gs * w4, nullptr) == hipSuccess;
+            for (uint64_t j = 0; ok && j < m; ++j)
+                ok = copy_rows_up(tmp + j * gs * w4, w4, db + (g + j) * n * rb, rb, n, nullptr) == hipSuccess;
+        }
+        ok = ok && dpfk::launch_slice_db(tmp, m * gs, w4, (uint8_t*)p + (g - g0) * gs * w4, nullptr) == hipSuccess &&
+             hipDeviceSynchronize() == hipSuccess;   // tmp is reused by the next chunk
+    }
+    (void)hipFree(tmp);
+    return ok ? DPF_OK : fail(DPF_ERR_HIP, "dpf: DB upload failed");
+}
+
+// dpf_pir_db_create_grouped: what needs no device, the devices, the uploads.
+int pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t caller_bytes, uint32_t logN,
+                          int ngpus, void** handle) {
+    if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
+    *handle = nullptr;
+    if (int rc = check_rec_bytes(RecRule::Bytes1, caller_bytes)) return rc;
+    if (logN > 63 || nrec > (1ull << logN)) return fail(DPF_ERR_PARAM, "dpf: group larger than 2^logN");
+    const size_t w4 = (caller_bytes + 3) & ~(size_t)3;
+    uint64_t bytes = 0;
+    if (!dpfh::grouped_bytes(ngroups, nrec, w4, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
+    if (ngroups > 0 && nrec > 0 && !db) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    int have = 0;
+    const DevList devs = pick_devs(0, &have);
+    if (have <= 0) return have;
+    const int want = ngpus <= 0 ? have : ngpus;
+    if (want > have) return fail(DPF_ERR_PARAM, "dpf: ngpus must be <= opened devices");
+    if (lds_shards()) return fail(DPF_ERR_PARAM, "dpf: grouped handles keep sliced shards only (DPF_PIR_FOLD=lds set)");
+    auto h = std::make_unique<PirDb>();
+    h->logN = logN;
+    h->nrec = ngroups * nrec;
+    h->rec_bytes = caller_bytes;
+    h->w4 = w4;
+    h->grouped = true;
+    h->ngroups = ngroups;
+    h->gnrec = nrec;
+    h->gps = dpfh::groups_per_shard(ngroups, (size_t)want);
+    h->ranges = dpfh::grouped_shards(ngroups, nrec, (size_t)want);
+    for (int g = 0; g < want; ++g)
+        if (int rc = upload_grouped_shard(h.get(), devs[(size_t)g], (size_t)g, db)) return rc;
+    *handle = h.release();
+    return DPF_OK;
+}
+
 // rule: RecRule::Mul32 (dpf_pir_db_create, _wide) or Bytes1 (_any and _sparse:
 // every width from 1 byte, shards at w4 bytes per record).  points: the
 // sparse kind (any device count; each shard with its points beside it).
@@ -173,8 +250,10 @@ int on_shard(PirDb* h, size_t s, const uint8_t* keys, size_t klen, size_t nkeys,
     std::lock_guard<std::mutex> lk(d.mu);
     DeviceGuard gd(d.id);
     HIP_TRY(d.keys.ensure(keys_bytes));
-    HIP_TRY(d.work.ensure(h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
-                                    : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+    // (The grouped workspace is a function of the key rows, groups x keys per group, alone.)
+    HIP_TRY(d.work.ensure(h->grouped  ? dpf_pir_grouped_workspace_size(1, nkeys, h->logN, h->w4)
+                          : h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
+                                      : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
     HIP_TRY(d.out.ensure(out_bytes));
     HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
     if (int rc = body(d)) return rc;
@@ -256,8 +335,9 @@ int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const uint8_
     if (n == 0) return DPF_OK;
     if (!idx || (!recs && !out)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
     dpfh::PirUpdatePlan plan;
-    if (!(h->sparse ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->ranges.slice, h->shard.size(), recs != nullptr, &plan)
-                    : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
+    if (!(h->grouped  ? dpfh::plan_pir_update_grouped(idx, n, h->ngroups, h->gnrec, h->shard.size(), recs != nullptr, &plan)
+          : h->sparse ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->ranges.slice, h->shard.size(), recs != nullptr, &plan)
+                      : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
         return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
     const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->w4);
     std::vector<uint8_t> host;
@@ -286,9 +366,17 @@ int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t
                              int ngpus, void** handle) {
     return pir_db_create(RecRule::Bytes1, points, true, db, nrec, rec_bytes, logN, ngpus, handle);
 }
+int dpf_pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes, uint32_t logN,
+                              int ngpus, void** handle) {
+    return pir_db_create_grouped(db, ngroups, nrec, rec_bytes, logN, ngpus, handle);
+}
 
 size_t dpf_pir_db_rec_bytes(void* handle) { return handle ? ((PirDb*)handle)->rec_bytes : 0; }
 uint64_t dpf_pir_db_nrec(void* handle) { return handle ? ((PirDb*)handle)->nrec : 0; }
+uint64_t dpf_pir_db_ngroups(void* handle) {
+    PirDb* h = (PirDb*)handle;
+    return !h ? 0 : h->grouped ? h->ngroups : 1;
+}
 void dpf_pir_db_free(void* handle) { delete (PirDb*)handle; }
 
 int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, uint8_t* ans) {
@@ -297,6 +385,28 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
     if (int rc = check_key(klen, h->logN)) return rc;
     const int g = (int)h->shard.size();
     const size_t rb = h->rec_bytes, w4 = h->w4;
+    if (h->grouped) {
+        // keys [ngroups][kpg]: every shard gets its groups' key rows and
+        // writes its groups' answers into their place; nothing to XOR.
+        if (h->ngroups == 0 ? nkeys != 0 : nkeys % h->ngroups != 0)
+            return fail(DPF_ERR_PARAM, "dpf: nkeys must be a multiple of the handle's groups");
+        if (nkeys == 0) return DPF_OK;
+        if (!keys || !ans) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+        const size_t kpg = nkeys / h->ngroups;
+        return shard((size_t)g, g, [&](int, size_t s, size_t) {
+            const uint64_t g0 = h->group_lo(s), ng = h->group_hi(s) - g0;
+            if (ng == 0) return (int)DPF_OK;
+            const size_t nk = ng * kpg;
+            return on_shard(h, s, keys + g0 * kpg * klen, klen, nk, nk * klen, std::max<size_t>(32, nk * w4), [&](Dev& d) {
+                if (int r = dpf_pir_answer_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
+                                                       (const uint8_t*)h->shard[s], h->gnrec, w4, (uint8_t*)d.out.p,
+                                                       d.work.p, d.st))
+                    return r;
+                HIP_TRY(copy_rows_down(ans + g0 * kpg * rb, d.out.p, w4, rb, nk, d.st));
+                return (int)DPF_OK;
+            });
+        });
+    }
     std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * rb));
     int rc = shard((size_t)g, g, [&](int, size_t s, size_t) {
         return on_shard(h, s, keys, klen, nkeys, std::max<size_t>(1, nkeys * klen), std::max<size_t>(32, nkeys * w4),
@@ -325,6 +435,8 @@ int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out) {
 int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, const uint8_t* msgs) {
     PirDb* h = (PirDb*)handle;
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (h->grouped)
+        return fail(DPF_ERR_PARAM, "dpf: dpf_pir_db_write does not take a grouped handle (a grouped private write is not built)");
     if (int rc = check_key(klen, h->logN)) return rc;
     if (nkeys == 0) return DPF_OK;
     if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");

@@ -1,0 +1,135 @@
+// pir_fold_grouped.hip — the grouped XOR fold: one launch answers many small
+// DBs (groups), each with its own keys.  The layout rule and the launch plan
+// are in pir_group_plan.hpp; the launcher walks the plan.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "dpf_kernels.hpp"
+#include "fold_ops.hpp"
+#include "pir_group_plan.hpp"
+#include "pir_kernels.hpp"
+
+namespace dpfk {
+
+// The popcount fold of k_fold_sliced_direct with a group coordinate.  Workgroup
+// x of the launch is unit u0 + x of the plan (dpfh::GroupedFoldPlan::unit): run
+// u % runs of column (u / runs) % C of group u / (runs * C), the group-local
+// super-groups [s0, s1) of that run.  Thread n of its 256 owns bit row n of the
+// column; per super-group it reads its 8 words once (the workgroup: 8 KiB
+// contiguous, flat super-group g * gsg + S) and, for each of the KP keys
+// k0 .. k0 + KP - 1 of the group, XORs (word & selection word) into that key's
+// accumulator: one v_bitop3 per word and key.  The selection words are
+// wave-uniform (scalar loads) from row g * kpg + k0 + j of bits; word 8 S + w
+// of a row is super-group S of the GROUP.  A row has wlim words: fewer than a
+// super-group's 8 at logN 7, and an end inside the last super-group whenever
+// the row is not a multiple of 256 bits; words past it select nothing.
+// Any width: thread n of column c has a row only if 256 c + n < nrows
+// (= 8 * rec_bytes); the others fold nothing, and an answer word 8 c + i >=
+// ntiles does not exist.
+// Answer bit n of key j is the parity of popcount(acc[j]): one ballot per key,
+// two words per wave.  atomic == 0 (one run per group): this workgroup is the
+// only writer of its words and stores them.  Otherwise the answers were
+// cleared earlier in stream order and the words are XORed in (vector atomics).
+template <int KP>
+__global__ __launch_bounds__(256) void k_fold_grouped(const uint32_t* __restrict__ bits, uint64_t wlim,
+                                                      const uint4* __restrict__ dbs, uint64_t gsg, uint32_t C,
+                                                      uint64_t runs, uint64_t spr, uint32_t kpg, uint32_t k0,
+                                                      uint32_t nrows, uint32_t ntiles, uint32_t* __restrict__ ans,
+                                                      uint64_t u0, uint32_t atomic) {
+    const uint32_t n = threadIdx.x, l = n & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t u = u0 + blockIdx.x;
+    const uint64_t run = u % runs, t = u / runs;
+    const uint64_t g = t / C;
+    const uint32_t col = (uint32_t)(t % C);
+    const uint64_t s0 = run * spr;
+    const uint64_t s1 = s0 + spr < gsg ? s0 + spr : gsg;
+    const uint64_t key0 = g * kpg + k0;                         // first answer / selection row of this pass
+    const uint32_t* sel = bits + key0 * wlim;
+    uint32_t acc[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) acc[j] = 0;
+    auto fold = [&](uint64_t S, const uint4& a, const uint4& b) __attribute__((always_inline)) {
+        const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        if (8 * S + 8 <= wlim) {                               // uniform
+#pragma unroll
+            for (int j = 0; j < KP; ++j)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[j] = xam(acc[j], x[q], sel[j * wlim + 8 * S + q]);
+        } else {                                               // the key rows end inside this super-group
+#pragma unroll
+            for (int j = 0; j < KP; ++j)
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    if (8 * S + q < wlim) acc[j] = xam(acc[j], x[q], sel[j * wlim + 8 * S + q]);
+        }
+    };
+    const uint64_t row = (uint64_t)col * 256 + n;
+    auto at = [&](uint64_t S) { return &dbs[((g * gsg + S) * nrows + row) * 2]; };
+    if (row < nrows) {
+        uint64_t S = s0;
+        for (; S + 1 < s1; S += 2) {
+            const uint4 a0 = at(S)[0], b0 = at(S)[1];
+            const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
+            fold(S, a0, b0);
+            fold(S + 1, a1, b1);
+        }
+        if (S < s1) fold(S, at(S)[0], at(S)[1]);
+    }
+    const uint32_t word = 8 * col + 2 * w + l;                  // lanes 0 and 1 of a wave: its two answer words
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc[j]) & 1) != 0);
+        if (l < 2 && word < ntiles) {
+            const uint32_t v = l ? (uint32_t)(m >> 32) : (uint32_t)m;
+            uint32_t* out = ans + (key0 + j) * ntiles + word;
+            if (!atomic) *out = v;
+            else if (v) atomicXor(out, v);
+        }
+    }
+}
+
+namespace {
+
+// DPF_GROUP_KP = 1 | 2 | 4: the widest key pass (measurement only).
+uint32_t group_kp_knob() {
+    static const uint32_t kp = [] {
+        const char* e = getenv("DPF_GROUP_KP");
+        return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 0u;
+    }();
+    return kp;
+}
+
+}  // namespace
+
+hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t ngroups,
+                                   uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, uint32_t* ans,
+                                   uint32_t* parts, hipStream_t st) {
+    (void)parts;   // the plan's launches write no scratch (dpfh::GroupedFoldPlan::scratch_bytes)
+    if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
+    if (ngroups == 0 || keys_per_group == 0) return hipSuccess;
+    if (ngroups * keys_per_group > UINT32_MAX) return hipErrorInvalidValue;
+    const uint64_t ans_bytes = ngroups * keys_per_group * rec_bytes;
+    if (nrec == 0) return hipMemsetAsync(ans, 0, ans_bytes, st);
+    if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
+    const uint64_t gsg = dpfh::group_stride(nrec) / 256;
+    const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
+    const dpfh::GroupedFoldPlan p = dpfh::plan_fold_grouped(ngroups, gsg, C, keys_per_group, (uint64_t)cu_count(),
+                                                            fold_limits(), group_kp_knob());
+    if (p.atomic())
+        if (hipError_t e = hipMemsetAsync(ans, 0, ans_bytes, st); e != hipSuccess) return e;
+    return p.for_each_launch([&](const dpfh::GroupLaunch& l) {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)l.blocks), dim3(256), 0, st, bits, words_per_key,
+                               reinterpret_cast<const uint4*>(dbs), p.gsg, p.C, p.runs, p.spr, p.kpg, l.k0,
+                               (uint32_t)(8 * rec_bytes), T, ans, l.u0, (uint32_t)p.atomic());
+        };
+        if (l.kp == 4) launch(k_fold_grouped<4>);
+        else if (l.kp == 2) launch(k_fold_grouped<2>);
+        else launch(k_fold_grouped<1>);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace dpfk

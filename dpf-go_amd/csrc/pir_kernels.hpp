@@ -53,6 +53,21 @@ hipError_t launch_slice_db(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes,
 hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t nrec,
                                   uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st);
 
+// The grouped fold (k_fold_grouped, pir_fold_grouped.hip): dbs is the sliced
+// layout (any width) of ngroups groups of nrec records, group g at flat record
+// g * dpfh::group_stride(nrec) with zero records behind its nrec
+// (pir_group_plan.hpp); bits is [ngroups * keys_per_group][words_per_key], row
+// g * keys_per_group + j selecting within group g (bit i = record i of the
+// group), and ans [ngroups * keys_per_group][rec_bytes] in the same order,
+// overwritten; zeros when nrec == 0.  The keys of a group share each read of
+// its tiles, up to 4 per pass.  words_per_key a multiple of 4 covering nrec
+// bits; ngroups * keys_per_group fits 32 bits.  `parts` is not written: runs
+// of one group combine by atomic XOR into answers cleared earlier in stream
+// order.  bits, dbs 16-byte, ans 4-byte aligned.
+hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t ngroups,
+                                   uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, uint32_t* ans,
+                                   uint32_t* parts, hipStream_t st);
+
 // Records of a resident DB changed and read back in place (k_update_sliced,
 // k_gather_sliced).  Update: record idx[i] := recs[i * rec_bytes ..) for
 // i < n, idx non-decreasing (of equal indices the last wins; unsorted input

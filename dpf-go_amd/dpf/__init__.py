@@ -102,6 +102,15 @@ SIGNATURES = {
     "dpf_pir_answer_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_write_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_create_sparse": (_int, [_u64p, _u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
+    "dpf_pir_group_stride": (_u64, [_u64]),
+    "dpf_pir_db_grouped_size": (_sz, [_u64, _u64, _sz]),
+    "dpf_pir_db_slice_grouped_dev": (_int, [_int, _vp, _u64, _u64, _sz, _vp, _vp]),
+    "dpf_xor_fold_grouped_workspace_size": (_sz, [_u64, _u64, _sz]),
+    "dpf_xor_fold_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_grouped_workspace_size": (_sz, [_u64, _u64, _u32, _sz]),
+    "dpf_pir_answer_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_db_create_grouped": (_int, [_u8p, _u64, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
+    "dpf_pir_db_ngroups": (_u64, [_vp]),
     "dpf_expand_keys_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp]),
     "dpf_evalfull_expanded_dev": (_int, [_int, _vp, _sz, _u32, _u32, _u64, _vp, _vp]),
     "dpf_forget_workspace": (_int, [_vp]),
@@ -790,6 +799,48 @@ def pir_write_sparse_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_points,
                                           _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work), _stream_handle(stream)))
 
 
+# ---- grouped PIR: ngroups small DBs of one shape, each with its own keys ----
+def pir_group_stride(nrec: int) -> int:
+    """Flat records a group of nrec records takes in the grouped layout: nrec rounded up to 256."""
+    return int(lib().dpf_pir_group_stride(nrec))
+
+
+def pir_db_grouped_size(ngroups: int, nrec: int, rec_bytes: int) -> int:
+    """Bytes of the grouped sliced layout (0 for a bad width or an overflowing product)."""
+    return int(lib().dpf_pir_db_grouped_size(ngroups, nrec, rec_bytes))
+
+
+def pir_db_slice_grouped_dev(d_db, ngroups: int, nrec: int, rec_bytes: int, d_dbs, device: int = 0, stream=None) -> None:
+    """The grouped layout of a row-major d_db [ngroups][nrec][rec_bytes]: group g,
+    record i at flat position g * pir_group_stride(nrec) + i of one sliced DB."""
+    _check(lib().dpf_pir_db_slice_grouped_dev(device, _ptr(d_db), ngroups, nrec, rec_bytes, _ptr(d_dbs),
+                                              _stream_handle(stream)))
+
+
+def xor_fold_grouped_workspace_size(ngroups: int, keys_per_group: int, rec_bytes: int) -> int:
+    return int(lib().dpf_xor_fold_grouped_workspace_size(ngroups, keys_per_group, rec_bytes))
+
+
+def xor_fold_grouped_dev(d_bits, bits_stride: int, ngroups: int, keys_per_group: int, d_dbs, nrec: int, rec_bytes: int,
+                         d_ans, d_work, device: int = 0, stream=None) -> None:
+    """Answers (ngroups * keys_per_group x rec_bytes): row g * keys_per_group + j
+    of d_bits selects among the nrec records of group g."""
+    _check(lib().dpf_xor_fold_grouped_dev(device, _ptr(d_bits), bits_stride, ngroups, keys_per_group, _ptr(d_dbs), nrec,
+                                          rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_grouped_workspace_size(ngroups: int, keys_per_group: int, logN: int, rec_bytes: int) -> int:
+    return int(lib().dpf_pir_grouped_workspace_size(ngroups, keys_per_group, logN, rec_bytes))
+
+
+def pir_answer_grouped_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: int, logN: int, d_dbs, nrec: int,
+                           rec_bytes: int, d_ans, d_work, device: int = 0, stream=None) -> None:
+    """One tree pass of all ngroups * keys_per_group keys (d_keys in group
+    order) over the 2^logN domain of a group, then xor_fold_grouped_dev."""
+    _check(lib().dpf_pir_answer_grouped_dev(device, _ptr(d_keys), key_len_, ngroups, keys_per_group, logN, _ptr(d_dbs),
+                                            nrec, rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -810,9 +861,16 @@ class PirDB:
     points[j] instead of at index j, points may repeat (such records are
     selected together), shards are record ranges over any number of GPUs, and
     update()/read() take a record's position in the list.  The points are
-    fixed at creation."""
+    fixed at creation.
 
-    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None):
+    With `groups=G` the handle is the grouped kind (dpf_pir_db_create_grouped):
+    db is [G * nrec, rec] or [G, nrec, rec], G DBs of one shape, each with its
+    own 2^logN domain and its own keys.  answer() takes keys [G * kpg, key_len]
+    in group order (row g * kpg + j queries group g) and returns the answers
+    in the same order; shards are ranges of whole groups over any number of
+    GPUs; update()/read() take idx = g * nrec + i; write() is refused."""
+
+    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None, groups=None):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
         if rec_bytes <= 0 or d.size % rec_bytes:
             raise ValueError("DB size must be a multiple of %d bytes" % rec_bytes)
@@ -820,7 +878,14 @@ class PirDB:
         self.rec_bytes = rec_bytes
         nrec = d.size // rec_bytes
         h = _vp()
-        if points is not None:
+        if groups is not None:
+            if points is not None:
+                raise ValueError("a PirDB is grouped or sparse, not both")
+            if groups < 0 or (nrec % groups if groups else nrec):
+                raise ValueError("the DB must hold the same number of records for each of %d groups" % groups)
+            _check(lib().dpf_pir_db_create_grouped(_buf(d), groups, nrec // groups if groups else 0, rec_bytes, logN,
+                                                   ngpus, ctypes.byref(h)))
+        elif points is not None:
             pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1)
             if pts.size != nrec:
                 raise ValueError("points must hold one uint64 per record")
@@ -840,6 +905,11 @@ class PirDB:
         Read-only, and 0 once the handle is closed: it used to be a plain
         attribute that kept the count given to the constructor."""
         return int(lib().dpf_pir_db_nrec(self._h))
+
+    @property
+    def ngroups(self) -> int:
+        """Groups of a grouped handle; 1 for the other kinds, 0 once closed (dpf_pir_db_ngroups)."""
+        return int(lib().dpf_pir_db_ngroups(self._h))
 
     def answer(self, keys: np.ndarray) -> np.ndarray:
         kk = np.ascontiguousarray(keys, dtype=np.uint8)

@@ -646,6 +646,79 @@ int dpf_pir_write_sparse_dev(int device, const uint8_t* d_keys, size_t key_len, 
 int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t nrec, size_t rec_bytes,
                              uint32_t logN, int ngpus, void** handle);
 
+/* ---- Grouped PIR: many small DBs, each with its own keys -----------------
+ * Every form above answers all keys of a batch against one DB.  A grouped DB
+ * is ngroups groups of nrec records of rec_bytes each, all of one shape (the
+ * owner pads a short group with zero records, which select nothing), and
+ * every group has its own keys_per_group keys over its own 2^logN domain: the
+ * buckets of a batch code (multi-query PIR: one key per bucket instead of one
+ * whole-domain key per wanted record), or many independent tables behind one
+ * server.  One fold launch has a group coordinate, so a batch costs launches
+ * by the batch and not by the group.
+ * Layout: no new format.  d_dbs is the any-width sliced layout of ONE flat DB
+ * in which group g, record i sits at flat position g * gs + i, with group
+ * stride gs = dpf_pir_group_stride(nrec) = nrec rounded up to a multiple of
+ * 256; flat positions [nrec, gs) of every group are zero records.
+ * dpf_pir_db_grouped_size is ngroups * gs * rec_bytes (at least 16; 0 for a
+ * width that is not a positive multiple of 4 up to DPF_PIR_MAX_REC_BYTES or a
+ * product that overflows).  dpf_pir_db_slice_grouped_dev builds it from the
+ * tightly packed d_db [ngroups][nrec][rec_bytes] (one slicing launch when
+ * nrec is a multiple of 256, else one per group: build time, not the hot
+ * path); dpf_pir_db_update_sliced_any_dev, _gather_ and the scatter work on it
+ * by flat position, with ngroups * gs as their nrec.
+ * dpf_xor_fold_grouped_dev: d_bits is [ngroups * keys_per_group][bits_stride]
+ * and row g * keys_per_group + j selects within group g (bit i = record i of
+ * the group; bits at positions >= nrec meet zero records only); d_ans
+ * [ngroups * keys_per_group][rec_bytes] in the same order, overwritten, zeros
+ * for nrec == 0.  bits_stride is a multiple of 16 with a bit for each of the
+ * nrec records.  d_work holds dpf_xor_fold_grouped_workspace_size(ngroups,
+ * keys_per_group, rec_bytes) bytes.  dpf_set_fold_limits' max_blocks, where
+ * below its default, caps the workgroups of each of its launches.
+ * dpf_pir_answer_grouped_dev: d_keys is [ngroups * keys_per_group][key_len] in
+ * that order; one tree pass of all the keys over the whole 2^logN domain into
+ * a bit area inside d_work, then the grouped fold.  DPF_PIR_FUSED has no part
+ * in it.  d_work holds dpf_pir_grouped_workspace_size(ngroups,
+ * keys_per_group, logN, rec_bytes) bytes: the tree workspace of all the keys
+ * (dpf_workspace_size) and their EvalFull rows (dpf_evalfull_len each), both
+ * rounded up to 256 bytes, and the grouped fold's workspace.  Both size
+ * functions are 0 for a bad width or a key count that does not fit 32 bits.
+ * Checked before any device call, in this order: rec_bytes (DPF_ERR_PARAM);
+ * for the answer the key (logN > 63 DPF_ERR_PARAM, then DPF_ERR_KEYLEN) and
+ * nrec > 2^logN, for the fold bits_stride (DPF_ERR_PARAM); ngroups *
+ * keys_per_group not fitting 32 bits (DPF_ERR_PARAM); null buffers the call
+ * has work for; misaligned buffers (d_dbs, d_bits and d_work 16-byte, d_ans
+ * 4-byte).  ngroups == 0 or keys_per_group == 0 returns DPF_OK without a
+ * launch.  Asynchronous on `stream`. */
+uint64_t dpf_pir_group_stride(uint64_t nrec);
+size_t dpf_pir_db_grouped_size(uint64_t ngroups, uint64_t nrec, size_t rec_bytes);
+int dpf_pir_db_slice_grouped_dev(int device, const uint8_t* d_db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes,
+                                 uint8_t* d_dbs, void* stream);
+size_t dpf_xor_fold_grouped_workspace_size(uint64_t ngroups, uint64_t keys_per_group, size_t rec_bytes);
+int dpf_xor_fold_grouped_dev(int device, const uint8_t* d_bits, size_t bits_stride, uint64_t ngroups,
+                             uint64_t keys_per_group, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                             uint8_t* d_ans, void* d_work, void* stream);
+size_t dpf_pir_grouped_workspace_size(uint64_t ngroups, uint64_t keys_per_group, uint32_t logN, size_t rec_bytes);
+int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
+                               uint64_t keys_per_group, uint32_t logN, const uint8_t* d_dbs, uint64_t nrec,
+                               size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream);
+/* A resident DB of the grouped kind: db [ngroups][nrec][rec_bytes], tightly
+ * packed, every width 1 .. DPF_PIR_MAX_REC_BYTES (padded to a multiple of 4
+ * on the device as dpf_pir_db_create_any does); logN <= 63 and nrec <= 2^logN
+ * (the domain of ONE group).  ngpus is any count up to the opened devices
+ * (<= 0: all of them): shard s holds the ceil(ngroups / ngpus) whole groups
+ * starting at s times that many.  dpf_pir_answer on the handle requires nkeys
+ * to be a multiple of ngroups (else DPF_ERR_PARAM): keys is [ngroups][kpg]
+ * and ans has the same order; each shard receives its groups' key rows and
+ * writes its groups' answers, with no host XOR.  dpf_pir_db_update and
+ * dpf_pir_db_read take idx = g * nrec + i, < ngroups * nrec, and keep their
+ * contracts; dpf_pir_db_nrec is ngroups * nrec.  dpf_pir_db_ngroups is the
+ * group count (1 for the other kinds of handle, 0 for NULL).
+ * dpf_pir_db_write on a grouped handle is DPF_ERR_PARAM: a grouped private
+ * write is not built.  With env DPF_PIR_FOLD=lds creation is DPF_ERR_PARAM. */
+int dpf_pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes, uint32_t logN,
+                              int ngpus, void** handle);
+uint64_t dpf_pir_db_ngroups(void* handle);
+
 #ifdef __cplusplus
 }
 #endif
