@@ -62,7 +62,7 @@ int pir_answer(RecRule rule, bool sliced, int device, const uint8_t* d_keys, siz
     hipStream_t st = (hipStream_t)stream;
     if (nkeys == 0) return DPF_OK;
     if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
         return DPF_OK;
     }
     const uint32_t stop = stop_of(logN);
@@ -352,7 +352,7 @@ int dpf_pir_answer_sparse_dev(int device, const uint8_t* d_keys, size_t klen, si
     CuScope cus(stream);
     hipStream_t st = (hipStream_t)stream;
     if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
         return DPF_OK;
     }
     const SparseWs w = sparse_ws(d_work, nkeys, nrec, logN);
@@ -451,7 +451,7 @@ int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t klen, u
     CuScope cus(stream);
     hipStream_t st = (hipStream_t)stream;
     if (nrec == 0) {
-        HIP_TRY(hipMemsetAsync(d_ans, 0, nkeys * rec_bytes, st));
+        HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
         return DPF_OK;
     }
     const uint32_t stop = stop_of(logN);

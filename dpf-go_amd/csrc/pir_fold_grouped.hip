@@ -111,14 +111,14 @@ hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key,
     if (ngroups == 0 || keys_per_group == 0) return hipSuccess;
     if (ngroups * keys_per_group > UINT32_MAX) return hipErrorInvalidValue;
     const uint64_t ans_bytes = ngroups * keys_per_group * rec_bytes;
-    if (nrec == 0) return hipMemsetAsync(ans, 0, ans_bytes, st);
+    if (nrec == 0) return launch_zero(ans, ans_bytes, st);
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
     const uint64_t gsg = dpfh::group_stride(nrec) / 256;
     const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
     const dpfh::GroupedFoldPlan p = dpfh::plan_fold_grouped(ngroups, gsg, C, keys_per_group, (uint64_t)cu_count(),
                                                             fold_limits(), group_kp_knob());
     if (p.atomic())
-        if (hipError_t e = hipMemsetAsync(ans, 0, ans_bytes, st); e != hipSuccess) return e;
+        if (hipError_t e = launch_zero(ans, ans_bytes, st); e != hipSuccess) return e;
     return p.for_each_launch([&](const dpfh::GroupLaunch& l) {
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3((uint32_t)l.blocks), dim3(256), 0, st, bits, words_per_key,

@@ -498,7 +498,7 @@ hipError_t launch_pir_fold(const uint32_t* bits, uint64_t words_per_key, const u
                            uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st) {
     if (nkeys == 0) return hipSuccess;
     if (rec_bytes == 0 || rec_bytes % 32 != 0) return hipErrorInvalidValue;
-    if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, st);
+    if (nrec == 0) return launch_zero(ans, (uint64_t)nkeys * rec_bytes, st);
     const FoldPlan p = plan_fold(rec_bytes, nkeys);
     const uint64_t rec_u4 = rec_bytes / 16, ans_words = rec_bytes / 4;
     const uint64_t cus = (uint64_t)cu_count(), cap = fold_limits().max_blocks;

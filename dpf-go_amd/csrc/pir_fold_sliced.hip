@@ -420,7 +420,7 @@ hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, 
                                   uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st) {
     if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
     if (nkeys == 0) return hipSuccess;
-    if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * rec_bytes, st);
+    if (nrec == 0) return launch_zero(ans, (uint64_t)nkeys * rec_bytes, st);
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
     const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
     const SlicedFold f{bits,  words_per_key, dbs,          (nrec + 255) / 256,   C, rec_bytes,

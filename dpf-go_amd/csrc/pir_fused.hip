@@ -361,7 +361,7 @@ hipError_t launch_pir_fused(const uint32_t* ek, uint32_t nkeys, uint32_t stop, u
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fz_timeout), &z, sizeof z);
         return hipErrorLaunchTimeOut;
     }
-    if (nrec == 0) return hipMemsetAsync(ans, 0, (size_t)nkeys * 32, st);
+    if (nrec == 0) return launch_zero(ans, (uint64_t)nkeys * 32, st);
     const uint64_t nsg = (nrec + 255) / 256;
     const uint32_t blocks = 1u << (stop - 1 - kFzBlockLog - prefix_bits);
     // DPF_PIR_FUSED_SYNC=1: producers and folders in lockstep (one workgroup

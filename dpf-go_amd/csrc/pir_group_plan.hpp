@@ -27,7 +27,7 @@
 //     set fewer than its default, else at most kGroupMaxBlocks;
 //   - the launches write no scratch: with one run per group (runs == 1) every
 //     answer word has exactly one writer, which stores it; with more, the
-//     answers are cleared by a memset node earlier in stream order and every
+//     answers are cleared by a zero-fill launch earlier in stream order and every
 //     run XORs its words in with one vector atomic each (XOR is order-free,
 //     so the answers are deterministic).  scratch_bytes() is therefore 0.
 #pragma once

@@ -71,6 +71,23 @@ hipError_t launch_xor_parts(const uint32_t* parts, uint64_t nparts, uint32_t nke
     return hipGetLastError();
 }
 
+// Answers are cleared on the caller's stream by a kernel, not by
+// hipMemsetAsync: in a stream capture that is a memset node, which does not
+// replay reliably ("Clearing answers"), while a kernel node
+// replays like every other launch of a _dev call.
+__global__ __launch_bounds__(256) void k_zero_words(uint32_t* __restrict__ p, uint64_t nwords) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (uint64_t)gridDim.x * 256) p[i] = 0u;
+}
+
+hipError_t launch_zero(void* p, uint64_t bytes, hipStream_t st) {
+    if (bytes == 0) return hipSuccess;
+    if (bytes % 4 != 0 || (uintptr_t)p % 4 != 0) return hipErrorInvalidValue;
+    const uint64_t nwords = bytes / 4, blocks = (nwords + 255) / 256;
+    hipLaunchKernelGGL(k_zero_words, dim3((uint32_t)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, (uint32_t*)p,
+                       nwords);
+    return hipGetLastError();
+}
+
 uint64_t pir_fold_parts_bytes() { return dpfh::kFoldPartsBytes; }
 
 // Tuning / test limits (set_fold_limits), both in one word so that a launcher

@@ -23,6 +23,10 @@ using dpfh::plan_fold;
 // pir_fold_parts_bytes() (per-workgroup partial answers).  bits, db 16-byte
 // aligned; words_per_key a multiple of 4 covering nrec bits.
 uint64_t pir_fold_parts_bytes();
+// `bytes` (a multiple of 4, p 4-byte aligned) of zeros on st: how every
+// launcher and _dev entry clears answers (a kernel, so that a stream capture
+// records no memset node; pir_kernels.hip, DESIGN.md §4.4 "Clearing answers").
+hipError_t launch_zero(void* p, uint64_t bytes, hipStream_t st);
 hipError_t launch_pir_fold(const uint32_t* bits, uint64_t words_per_key, const uint8_t* db, uint64_t nrec,
                            uint64_t rec_bytes, uint32_t nkeys, uint32_t* ans, uint32_t* parts, hipStream_t st);
 

@@ -119,7 +119,9 @@ int dpf_evalfull_split(const uint8_t* key, size_t key_len, uint32_t logN, uint8_
 /* ---- evaluation, device-resident buffers (asynchronous on `stream`) ----
  * Pointers are device pointers on `device`; `work` holds
  * dpf_workspace_size(nkeys, logN) bytes; stream is a hipStream_t (NULL =
- * the default stream).  Nothing is synchronised. */
+ * the default stream).  Nothing is synchronised.  After one eager call of
+ * the same shape, a _dev call may be recorded in a stream capture and
+ * replayed over new buffer contents (tests/test_gpu_stream_capture.py). */
 int dpf_evalfull_batch_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
                            uint8_t* d_out, void* d_work, void* stream);
 /* The subtree at depth prefix_bits, index prefix of every key: 2^(logN-3-
@@ -351,7 +353,9 @@ int dpf_xor_fold_dev(int device, const uint8_t* d_bits, size_t bits_stride, size
  * DB (nrec x 32 B) into dpf_pir_db_sliced_size(nrec) bytes.  The _sliced
  * entry points take that layout and give the same answers as their row-major
  * forms (same workspace sizes); 32-byte records (wider ones: the _wide
- * entry points below). */
+ * entry points below).  dpf_pir_answer_sliced_dev can be recorded in a stream
+ * capture only under DPF_PIR_SPLIT, the default: where dpf_set_pir_kernel
+ * (below) selected the fused kernel, its launcher synchronises first. */
 size_t dpf_pir_db_sliced_size(uint64_t nrec);
 int dpf_pir_db_slice_dev(int device, const uint8_t* d_db, uint64_t nrec, uint8_t* d_dbs, void* stream);
 int dpf_pir_answer_sliced_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
@@ -533,7 +537,10 @@ int dpf_set_fold_limits(uint32_t max_blocks, uint32_t max_sg_per_block);
  * linked only into the experimental library (make -C dpf-go_amd
  * experimental: the product library's objects plus csrc/pir_fused.hip and
  * csrc/eval_trie.hip): the product library returns DPF_ERR_PARAM for DPF_PIR_FUSED and
- * DPF_PIR_FUSED_ANY.  Process-wide; env DPF_PIR_KERNEL=split|fused|fused-any. */
+ * DPF_PIR_FUSED_ANY.  The fused launcher reads a device symbol synchronously
+ * before it launches, so a call that takes the fused choice cannot be recorded
+ * in a stream capture; the split path can.  Process-wide; env
+ * DPF_PIR_KERNEL=split|fused|fused-any. */
 #define DPF_PIR_SPLIT 0
 #define DPF_PIR_FUSED 1
 #define DPF_PIR_FUSED_ANY 2
