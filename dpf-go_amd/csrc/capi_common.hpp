@@ -4,7 +4,8 @@
 //   capi_pir.hip     every device-resident PIR form (slice, fold, scatter,
 //                    answer, write, update / gather, the sparse composites,
 //                    the grouped forms)
-//   capi_pir_db.hip  the resident-DB handle (create, answer, update / read, write)
+//   capi_pir_db.hip  the resident-DB handle (create, answer, update / read, write,
+//                    the grouped write)
 // Here: the error slot, the device objects, and one definition of each
 // workspace layout and of each argument rule.  An entry point is a short list
 // of these rules in its own order of reports (the folds check alignment before

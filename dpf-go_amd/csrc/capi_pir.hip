@@ -462,4 +462,71 @@ int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t klen, u
     return DPF_OK;
 }
 
+// ---- grouped private writes: the dual of the grouped fold ----
+// The scatter has a group coordinate (launch_scatter_grouped), or loops the
+// dense scatter over the groups where its plan says so; no workspace.
+int dpf_xor_scatter_grouped_dev(int device, const uint8_t* d_bits, size_t bits_stride, uint64_t ngroups,
+                                uint64_t keys_per_group, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec,
+                                size_t rec_bytes, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_sel_bits(bits_stride, nrec)) return rc;
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    if (!present(d_bits, d_msgs, d_dbs)) return null_buffer();
+    if (!aligned(16, d_bits, d_msgs, d_dbs)) return misaligned_buffer();
+    if (ngroups == 0 || keys_per_group == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(dpfk::launch_scatter_grouped((const uint32_t*)d_bits, bits_stride / 4, d_dbs, ngroups,
+                                         (uint32_t)keys_per_group, nrec, rec_bytes, d_msgs, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_pir_write_grouped_dev(int device, const uint8_t* d_keys, size_t klen, uint64_t ngroups, uint64_t keys_per_group,
+                              uint32_t logN, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                              void* d_work, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_subtree(klen, logN, 0, 0, nrec)) return rc;   // the key, then nrec <= 2^logN
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    if (!present(d_keys, d_msgs, d_dbs, d_work)) return null_buffer();
+    if (!aligned(16, d_msgs, d_dbs, d_work)) return misaligned_buffer();
+    const size_t nkeys = ngroups * keys_per_group;
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t stop = stop_of(logN);
+    const GroupWs w = group_ws(d_work, nkeys, stop);   // the answer's layout; the fold's scratch stays unused
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, 0, 0, w.bits, w.per_key, d_work, st, want_bs()));
+    HIP_TRY(dpfk::launch_scatter_grouped((const uint32_t*)w.bits, w.per_key / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
+                                         nrec, rec_bytes, d_msgs, st));
+    return DPF_OK;
+}
+
+int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
+                                 dpf_scatter_grouped_form* form) {
+    if (form == nullptr || !rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK ||
+        nrec > UINT64_MAX - 255)
+        return fail(DPF_ERR_PARAM, "dpf: form query out of range");
+    const dpfh::GroupedScatterPlan p = dpfk::scatter_grouped_plan(ngroups, (uint32_t)keys_per_group, nrec, rec_bytes,
+                                                                  (uint64_t)(cus > 0 ? cus : 0));
+    memset(form, 0, sizeof *form);
+    form->route = (uint32_t)p.route;
+    form->columns = p.C;
+    form->runs = p.runs;
+    form->sg_per_run = p.spr;
+    form->units = p.units();
+    form->max_blocks = p.cap;
+    form->passes = p.passes();
+    uint64_t launches = 0;
+    uint32_t widths = 0;
+    p.for_each_launch([&](const dpfh::GroupScatterLaunch& l) {
+        ++launches;
+        if (l.u0 == 0) widths |= 1u << (l.kp - 1);
+        return 0;
+    });
+    form->launches = launches;
+    form->pass_widths = widths;
+    return DPF_OK;
+}
+
 }  // extern "C"

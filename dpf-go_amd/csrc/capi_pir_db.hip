@@ -239,7 +239,7 @@ int pir_db_create(RecRule rule, const uint64_t* points, bool sparse, const uint8
     return DPF_OK;
 }
 
-// One shard's turn in dpf_pir_answer / dpf_pir_db_write: under its device's
+// One shard's turn in dpf_pir_answer / dpf_pir_db_write(_grouped): under its device's
 // mutex and on its device, staging of at least keys_bytes / out_bytes and the
 // workspace of the shard's device form, the keys up, then body(d) and the
 // stream drained, so a concurrent call sees the shard before or after.
@@ -436,7 +436,7 @@ int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkey
     PirDb* h = (PirDb*)handle;
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
     if (h->grouped)
-        return fail(DPF_ERR_PARAM, "dpf: dpf_pir_db_write does not take a grouped handle (a grouped private write is not built)");
+        return fail(DPF_ERR_PARAM, "dpf: dpf_pir_db_write does not take a grouped handle (use dpf_pir_db_write_grouped)");
     if (int rc = check_key(klen, h->logN)) return rc;
     if (nkeys == 0) return DPF_OK;
     if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
@@ -447,6 +447,31 @@ int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t klen, size_t nkey
         return on_shard(h, s, keys, klen, nkeys, nkeys * klen, nkeys * w4, [&](Dev& d) {
             HIP_TRY(copy_rows_up(d.out.p, w4, msgs, rb, nkeys, d.st));   // zero pad bytes: the DB's stay zero
             return shard_dev(h, s, d, klen, nkeys, true);
+        });
+    });
+}
+
+// The grouped private write: keys and msgs [ngroups][kpg]; shard s gets its
+// groups' key and message rows and applies them to its groups.
+int dpf_pir_db_write_grouped(void* handle, const uint8_t* keys, size_t klen, size_t nkeys, const uint8_t* msgs) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    if (!h->grouped) return fail(DPF_ERR_PARAM, "dpf: dpf_pir_db_write_grouped takes a grouped handle only");
+    if (int rc = check_key(klen, h->logN)) return rc;
+    if (h->ngroups == 0 ? nkeys != 0 : nkeys % h->ngroups != 0)
+        return fail(DPF_ERR_PARAM, "dpf: nkeys must be a multiple of the handle's groups");
+    if (nkeys == 0) return DPF_OK;
+    if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    const int g = (int)h->shard.size();
+    const size_t rb = h->rec_bytes, w4 = h->w4, kpg = nkeys / h->ngroups;
+    return shard((size_t)g, g, [&](int, size_t s, size_t) {
+        const uint64_t g0 = h->group_lo(s), ng = h->group_hi(s) - g0;
+        if (ng == 0 || h->gnrec == 0) return (int)DPF_OK;
+        const size_t nk = ng * kpg;
+        return on_shard(h, s, keys + g0 * kpg * klen, klen, nk, nk * klen, std::max<size_t>(32, nk * w4), [&](Dev& d) {
+            HIP_TRY(copy_rows_up(d.out.p, w4, msgs + g0 * kpg * rb, rb, nk, d.st));   // zero pad bytes: the DB's stay zero
+            return dpf_pir_write_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
+                                             (const uint8_t*)d.out.p, (uint8_t*)h->shard[s], h->gnrec, w4, d.work.p, d.st);
         });
     });
 }

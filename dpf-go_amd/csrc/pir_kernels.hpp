@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "pir_fold_plan.hpp"
+#include "pir_group_scatter_plan.hpp"
 
 namespace dpfk {
 
@@ -103,6 +104,28 @@ hipError_t launch_scatter_sliced(const uint32_t* bits, uint64_t words_per_key, u
                                  uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st);
 hipError_t launch_scatter_rows(const uint32_t* bits, uint64_t words_per_key, uint8_t* db, uint64_t nrec,
                                uint64_t rec_bytes, const uint8_t* msgs, uint64_t nkeys, hipStream_t st);
+
+// The grouped private write, the dual of the grouped fold (k_scatter_grouped,
+// pir_scatter_grouped.hip): dbs is the grouped layout above, bits and msgs are
+// [ngroups * keys_per_group] rows in group order, and for i < nrec
+//   group g, record i ^= XOR over k < keys_per_group with bit i of
+//   bits[(g * keys_per_group + k) * words_per_key ...] set of
+//   msgs[(g * keys_per_group + k) * rec_bytes ..).
+// Bits at positions >= nrec are ignored, so the zero records behind every
+// group's nrec stay zero; words past a row's end are not read.  Planned by
+// pir_group_scatter_plan.hpp under set_fold_limits' max_blocks and max_sg:
+// key passes of 4 and a last one of 1 to 3 over one grid of all groups, or (the plan's route
+// rule; few large groups with many keys) a loop of launch_scatter_sliced over
+// each group's flat range.  No workspace, no atomics, asynchronous on st.
+// bits, dbs and msgs 16-byte aligned; words_per_key a multiple of 4 covering
+// nrec bits; ngroups * keys_per_group fits 32 bits.
+hipError_t launch_scatter_grouped(const uint32_t* bits, uint64_t words_per_key, uint8_t* dbs, uint64_t ngroups,
+                                  uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, const uint8_t* msgs,
+                                  hipStream_t st);
+// The plan that call walks: under the current limits, on `cus` CUs (0: the
+// calling thread's budget), its route after the DPF_GROUP_SCATTER_ROUTE knob.
+dpfh::GroupedScatterPlan scatter_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec,
+                                              uint64_t rec_bytes, uint64_t cus);
 
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per

@@ -68,6 +68,12 @@ class EvalFormC(ctypes.Structure):
                 ("ragged", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2), ("grid", _u64), ("nodes", TreeFormC)]
 
 
+class ScatterGroupedFormC(ctypes.Structure):
+    """dpf_scatter_grouped_form (include/dpf_hip.h)."""
+    _fields_ = [("route", _u32), ("columns", _u32), ("pass_widths", _u32), ("pad_", _u32), ("runs", _u64),
+                ("sg_per_run", _u64), ("units", _u64), ("max_blocks", _u64), ("passes", _u64), ("launches", _u64)]
+
+
 # name -> (restype, argtypes); must cover every function in include/dpf_hip.h
 SIGNATURES = {
     "dpf_tree_form_for": (_int, [_sz, _u32, _u32, _u32, _int, ctypes.POINTER(TreeFormC)]),
@@ -111,6 +117,10 @@ SIGNATURES = {
     "dpf_pir_answer_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_db_create_grouped": (_int, [_u8p, _u64, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_ngroups": (_u64, [_vp]),
+    "dpf_xor_scatter_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _vp, _vp, _u64, _sz, _vp]),
+    "dpf_pir_write_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_write_grouped": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
+    "dpf_scatter_grouped_form_for": (_int, [_u64, _u64, _u64, _sz, _int, ctypes.POINTER(ScatterGroupedFormC)]),
     "dpf_expand_keys_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp]),
     "dpf_evalfull_expanded_dev": (_int, [_int, _vp, _sz, _u32, _u32, _u64, _vp, _vp]),
     "dpf_forget_workspace": (_int, [_vp]),
@@ -841,6 +851,38 @@ def pir_answer_grouped_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: 
                                             nrec, rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
 
 
+SCATTER_GROUPED, SCATTER_LOOP = 0, 1
+ScatterGroupedForm = collections.namedtuple(
+    "ScatterGroupedForm", "route columns pass_widths runs sg_per_run units max_blocks passes launches")
+
+
+def xor_scatter_grouped_dev(d_bits, bits_stride: int, ngroups: int, keys_per_group: int, d_msgs, d_dbs, nrec: int,
+                            rec_bytes: int, device: int = 0, stream=None) -> None:
+    """The dual of xor_fold_grouped_dev: group g, record i ^= XOR of the
+    messages d_msgs[g * keys_per_group + k] whose row of d_bits has bit i set.
+    The zero records behind every group's nrec stay zero.  No workspace."""
+    _check(lib().dpf_xor_scatter_grouped_dev(device, _ptr(d_bits), bits_stride, ngroups, keys_per_group, _ptr(d_msgs),
+                                             _ptr(d_dbs), nrec, rec_bytes, _stream_handle(stream)))
+
+
+def pir_write_grouped_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: int, logN: int, d_msgs, d_dbs,
+                          nrec: int, rec_bytes: int, d_work, device: int = 0, stream=None) -> None:
+    """One tree pass of all ngroups * keys_per_group keys (group order) over a
+    group's 2^logN domain, then xor_scatter_grouped_dev.  d_work holds
+    pir_grouped_workspace_size bytes."""
+    _check(lib().dpf_pir_write_grouped_dev(device, _ptr(d_keys), key_len_, ngroups, keys_per_group, logN, _ptr(d_msgs),
+                                           _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work), _stream_handle(stream)))
+
+
+def scatter_grouped_form_for(ngroups: int, keys_per_group: int, nrec: int, rec_bytes: int,
+                             cus: int = 0) -> "ScatterGroupedForm":
+    """What xor_scatter_grouped_dev launches for this shape under the current
+    fold limits (dpf_scatter_grouped_form_for).  Needs no device when cus > 0."""
+    c = ScatterGroupedFormC()
+    _check(lib().dpf_scatter_grouped_form_for(ngroups, keys_per_group, nrec, rec_bytes, cus, ctypes.byref(c)))
+    return ScatterGroupedForm(*[int(getattr(c, f)) for f in ScatterGroupedForm._fields])
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -868,7 +910,8 @@ class PirDB:
     own 2^logN domain and its own keys.  answer() takes keys [G * kpg, key_len]
     in group order (row g * kpg + j queries group g) and returns the answers
     in the same order; shards are ranges of whole groups over any number of
-    GPUs; update()/read() take idx = g * nrec + i; write() is refused."""
+    GPUs; update()/read() take idx = g * nrec + i; write() is refused, the
+    private write of a grouped handle is write_grouped()."""
 
     def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None, groups=None):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
@@ -941,6 +984,21 @@ class PirDB:
         if m.size != kk.shape[0] * self.rec_bytes:
             raise ValueError("msgs must hold len(keys) messages of %d bytes" % self.rec_bytes)
         _check(lib().dpf_pir_db_write(self._h, _buf(kk), kk.shape[1], kk.shape[0], _buf(m)))
+
+    def write_grouped(self, keys, msgs) -> None:
+        """Private write of a grouped handle: keys [G * kpg, key_len] and msgs
+        [G * kpg, rec_bytes] in group order; record i of group g ^= XOR of the
+        messages of group g's keys whose EvalFull has bit i set.  A key with
+        an all-zero message is a dummy.  A key count that is no multiple of
+        the groups, a handle that is not grouped or a short key raises
+        DPFPanic and changes nothing."""
+        kk = np.ascontiguousarray(keys, dtype=np.uint8)
+        if kk.ndim != 2:
+            raise ValueError("keys must be a (nkeys, key_len) array")
+        m = np.ascontiguousarray(msgs, dtype=np.uint8).reshape(-1)
+        if m.size != kk.shape[0] * self.rec_bytes:
+            raise ValueError("msgs must hold len(keys) messages of %d bytes" % self.rec_bytes)
+        _check(lib().dpf_pir_db_write_grouped(self._h, _buf(kk), kk.shape[1], kk.shape[0], _buf(m)))
 
     def read(self, idx) -> np.ndarray:
         """The records idx[i] as the DB now holds them, (len(idx), rec_bytes), in the caller's order."""

@@ -9,6 +9,12 @@ domain: a dummy point in the buckets it does not use, so the servers learn
 nothing from which buckets are queried.  On the server the buckets are the
 groups of `dpf.PirDB(bucket_db, logN, rec_bytes=rec, groups=nbuckets)`.
 
+A private write is the other way round: the table is kept consistent only if
+every replica of a changed record changes, so a client that XORs deltas into m
+records sends kpg short keys per bucket (write_plan: one per replica that falls
+into the bucket, dummies with an all-zero message in the unused slots) to
+`PirDB.write_grouped`, instead of m keys over the whole domain per replica.
+
 This is documentation that runs, not a protocol implementation: host-only,
 numpy-only, with a fixed integer mix in the place of a keyed hash, no
 treatment of failure probability and no padding of the number of queries.
@@ -23,7 +29,8 @@ _M = (1 << 64) - 1
 
 
 class BucketOverflow(Exception):
-    """assign() found no placement within its bound on cuckoo kicks."""
+    """assign() found no placement within its bound on cuckoo kicks, or
+    write_plan() a bucket that needs more keys than it was given."""
 
 
 class Layout(NamedTuple):
@@ -99,3 +106,33 @@ def alphas(assignment: dict, lay: Layout) -> np.ndarray:
         j = [int(x) for x in lay.bucket[rec]].index(b)
         a[b] = lay.pos[rec, j]
     return a
+
+
+def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None):
+    """(alphas [nbuckets][kpg] uint64, msgs [nbuckets][kpg][rec] uint8) for
+    `PirDB.write_grouped`: {record: XOR delta (rec bytes)} turned into one key
+    slot per replica of every record, at the replica's position in its bucket
+    with the delta as its message.  Unused slots are dummies: point 0 with an
+    all-zero message, which changes nothing, so the servers learn nothing from
+    which buckets are written.  rec_bytes is the record width; it may be left
+    out where deltas is not empty (an empty one with rec_bytes is an all-dummy
+    batch, cover traffic).  Raises BucketOverflow when a bucket holds more
+    replicas of the changed records than kpg."""
+    items = [(int(r), np.ascontiguousarray(d, dtype=np.uint8).reshape(-1)) for r, d in deltas.items()]
+    if rec_bytes is None and not items:
+        raise ValueError("rec_bytes is needed where there are no deltas to take the width from")
+    rec = int(rec_bytes) if rec_bytes is not None else items[0][1].size
+    al = np.zeros((lay.nbuckets, kpg), np.uint64)
+    msgs = np.zeros((lay.nbuckets, kpg, rec), np.uint8)
+    used = np.zeros(lay.nbuckets, np.int64)
+    for r, d in items:
+        if d.size != rec:
+            raise ValueError("every delta must be %d bytes wide" % rec)
+        for j in range(lay.bucket.shape[1]):
+            b = int(lay.bucket[r, j])
+            if used[b] == kpg:
+                raise BucketOverflow("bucket %d needs more than %d keys" % (b, kpg))
+            al[b, used[b]] = lay.pos[r, j]
+            msgs[b, used[b]] = d
+            used[b] += 1
+    return al, msgs

@@ -720,11 +720,85 @@ int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t key_len
  * dpf_pir_db_read take idx = g * nrec + i, < ngroups * nrec, and keep their
  * contracts; dpf_pir_db_nrec is ngroups * nrec.  dpf_pir_db_ngroups is the
  * group count (1 for the other kinds of handle, 0 for NULL).
- * dpf_pir_db_write on a grouped handle is DPF_ERR_PARAM: a grouped private
- * write is not built.  With env DPF_PIR_FOLD=lds creation is DPF_ERR_PARAM. */
+ * dpf_pir_db_write on a grouped handle is DPF_ERR_PARAM (its keys are one
+ * batch over one DB): the grouped private write is dpf_pir_db_write_grouped
+ * below.  With env DPF_PIR_FOLD=lds creation is DPF_ERR_PARAM. */
 int dpf_pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes, uint32_t logN,
                               int ngpus, void** handle);
 uint64_t dpf_pir_db_ngroups(void* handle);
+
+/* ---- Grouped private writes: the dual of the grouped fold ----------------
+ * d_bits and d_msgs are [ngroups * keys_per_group] rows in group order, and
+ * for i < nrec
+ *   group g, record i ^= XOR over k < keys_per_group, with bit i of
+ *                        d_bits row g * keys_per_group + k set,
+ *                        of d_msgs row g * keys_per_group + k.
+ * Bit i of a row is bit i of the GROUP's domain, as in the grouped fold.  Flat
+ * positions [nrec, dpf_pir_group_stride(nrec)) of every group stay zero
+ * whatever the caller left in the bits past nrec, and a row's words past its
+ * end are not read.  A key with an all-zero message is a dummy and changes
+ * nothing.  Two servers that apply the same messages under their shares of the
+ * keys change the XOR of their DBs by message k at (g, alpha_k) only.
+ * dpf_xor_scatter_grouped_dev: caller-made bits, bits_stride a multiple of 16
+ * with a bit for each of the nrec records; no workspace.  One 1-D launch per
+ * key pass (4 keys of every group, the last pass the 1 to 3 left: kpg keys are
+ * ceil(kpg / 4) passes over the DB) covers all groups; few large groups
+ * with many keys each go through one dense scatter per group instead (the
+ * plan's route rule, csrc/pir_group_scatter_plan.hpp).  dpf_set_fold_limits'
+ * max_blocks, where below its default, caps the workgroups of each launch, and
+ * max_sg_per_block the super-groups a workgroup rewrites.  Env
+ * DPF_GROUP_SCATTER_ROUTE=grouped|loop, read at every call, forces the route
+ * for every caller of these entries (measurement only; leave it unset).
+ * dpf_pir_write_grouped_dev: d_keys is [ngroups * keys_per_group][key_len] in
+ * that order; one tree pass of all the keys over the whole 2^logN domain into
+ * the bit area inside d_work, then the grouped scatter.  d_work holds
+ * dpf_pir_grouped_workspace_size(ngroups, keys_per_group, logN, rec_bytes)
+ * bytes, the answer's workspace.  Both AES back ends; DPF_PIR_FUSED has no
+ * part in it.
+ * Checked before any device call, in this order: rec_bytes (DPF_ERR_PARAM);
+ * for the scatter bits_stride, for the write the key (logN > 63 DPF_ERR_PARAM,
+ * then DPF_ERR_KEYLEN) and nrec > 2^logN (DPF_ERR_PARAM); ngroups *
+ * keys_per_group not fitting 32 bits; a null buffer (every buffer must be
+ * given, as for the other scatters); a buffer that is not 16-byte aligned
+ * (d_bits, d_msgs, d_dbs, d_work).  ngroups == 0, keys_per_group == 0 or
+ * nrec == 0 then returns DPF_OK without a launch.  Both are asynchronous on
+ * `stream` and can be captured: no synchronisation, no allocation, no memset. */
+int dpf_xor_scatter_grouped_dev(int device, const uint8_t* d_bits, size_t bits_stride, uint64_t ngroups,
+                                uint64_t keys_per_group, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec,
+                                size_t rec_bytes, void* stream);
+int dpf_pir_write_grouped_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
+                              uint64_t keys_per_group, uint32_t logN, const uint8_t* d_msgs, uint8_t* d_dbs,
+                              uint64_t nrec, size_t rec_bytes, void* d_work, void* stream);
+/* The private write of a grouped handle: keys [nkeys][key_len] and msgs
+ * [nkeys][dpf_pir_db_rec_bytes(handle)], nkeys = ngroups * kpg in group order
+ * (row g * kpg + j writes into group g); nkeys not a multiple of the handle's
+ * groups is DPF_ERR_PARAM, a handle that is not grouped is DPF_ERR_PARAM, a
+ * short key is DPF_ERR_KEYLEN, and nothing is changed.  Shard s receives only
+ * its groups' key and message rows and runs dpf_pir_write_grouped_dev on its
+ * device's stream under that device's mutex, with dpf_pir_db_write's
+ * guarantees towards concurrent calls.  Synchronous. */
+int dpf_pir_db_write_grouped(void* handle, const uint8_t* keys, size_t key_len, size_t nkeys, const uint8_t* msgs);
+/* What dpf_xor_scatter_grouped_dev launches for a shape under the current
+ * dpf_set_fold_limits, on `cus` CUs (<= 0: the current device's / the calling
+ * thread's stream budget; needs no device when cus > 0) and, like the call
+ * itself, under env DPF_GROUP_SCATTER_ROUTE where set.  DPF_ERR_PARAM for a
+ * bad width or a key count that does not fit 32 bits. */
+#define DPF_SCATTER_GROUPED 0 /* the grouped kernel, one launch per key pass */
+#define DPF_SCATTER_LOOP 1    /* one dense scatter per group */
+typedef struct dpf_scatter_grouped_form {
+    uint32_t route;       /* DPF_SCATTER_* above; the fields below describe the grouped kernel's launches */
+    uint32_t columns;     /* 32-byte columns of a record, the last one possibly short */
+    uint32_t pass_widths; /* bit w - 1 set: a key pass of width w (1 .. 4) is used */
+    uint32_t pad_;
+    uint64_t runs;        /* workgroups per (group, column) */
+    uint64_t sg_per_run;  /* super-groups per run (the last run: what is left) */
+    uint64_t units;       /* workgroups per key pass */
+    uint64_t max_blocks;  /* workgroups per launch at the most */
+    uint64_t passes;      /* key passes */
+    uint64_t launches;    /* launches of all passes */
+} dpf_scatter_grouped_form;
+int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
+                                 dpf_scatter_grouped_form* form);
 
 #ifdef __cplusplus
 }
