@@ -1,11 +1,11 @@
 // capi_common.hpp — what the translation units of the C ABI share (internal).
 //   dpf_capi.hip     the device registry and the knobs, the staging pipeline,
 //                    the tree, Eval and Eval-bits entries, the form queries
-//   capi_pir.hip     every device-resident PIR form (slice, fold, scatter,
+//   capi_pir.hip     every device-resident PIR form (slice and un-slice, fold, scatter,
 //                    answer, write, update / gather, the sparse composites,
 //                    the grouped forms)
 //   capi_pir_db.hip  the resident-DB handle (create, answer, update / read, write,
-//                    the grouped write)
+//                    the grouped write, export / merge / clear)
 // Here: the error slot, the device objects, and one definition of each
 // workspace layout and of each argument rule.  An entry point is a short list
 // of these rules in its own order of reports (the folds check alignment before

@@ -1,5 +1,5 @@
 // capi_pir.hip — the device-resident PIR forms of the C ABI (include/dpf_hip.h):
-// slicing a DB, the XOR fold and its dual the XOR scatter over caller-made
+// slicing a DB and un-slicing it again, the XOR fold and its dual the XOR scatter over caller-made
 // selection bits, the composites that make the bits themselves (a subtree
 // EvalFull, or for a sparse key set an Eval at the records' points), and the
 // in-place update / gather of records.  All enqueue on the caller's stream.
@@ -407,6 +407,52 @@ int dpf_pir_db_slice_grouped_dev(int device, const uint8_t* d_db, uint64_t ngrou
     }
     for (uint64_t i = 0; i < ngroups; ++i)   // a group's last super-group is zero-filled behind its nrec records
         HIP_TRY(dpfk::launch_slice_db(d_db + i * nrec * rec_bytes, nrec, rec_bytes, d_dbs + i * gs * rec_bytes, st));
+    return DPF_OK;
+}
+
+// ---- the whole-DB read-out: un-slice, and the merge of two sliced buffers ----
+// The inverse of the two slice entries above, with their rules in their order:
+// width, the products, null, alignment.
+int dpf_pir_db_unslice_any_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_db,
+                               void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    uint64_t bytes = 0;
+    if (!dpfh::grouped_bytes(1, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: DB too large");
+    if (bytes > 0 && !present(d_dbs, d_db)) return null_buffer();
+    if (!aligned(16, d_dbs, d_db)) return misaligned_buffer();
+    if (bytes == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_unslice_db(d_dbs, nrec, rec_bytes, d_db, (hipStream_t)stream));
+    return DPF_OK;
+}
+
+int dpf_pir_db_unslice_grouped_dev(int device, const uint8_t* d_dbs, uint64_t ngroups, uint64_t nrec, size_t rec_bytes,
+                                   uint8_t* d_db, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    uint64_t bytes = 0;
+    if (!dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
+    if (bytes > 0 && !present(d_dbs, d_db)) return null_buffer();
+    if (!aligned(16, d_dbs, d_db)) return misaligned_buffer();
+    if (bytes == 0) return DPF_OK;
+    DeviceGuard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t gs = dpfh::group_stride(nrec);
+    if (gs == nrec) {   // no padding: the flat DB is the row-major one
+        HIP_TRY(dpfk::launch_unslice_db(d_dbs, ngroups * nrec, rec_bytes, d_db, st));
+        return DPF_OK;
+    }
+    for (uint64_t i = 0; i < ngroups; ++i)   // the zero records behind a group's nrec are not written
+        HIP_TRY(dpfk::launch_unslice_db(d_dbs + i * gs * rec_bytes, nrec, rec_bytes, d_db + i * nrec * rec_bytes, st));
+    return DPF_OK;
+}
+
+int dpf_pir_db_xor_sliced_dev(int device, uint8_t* d_dbs, const uint8_t* d_other, size_t bytes, void* stream) {
+    if (bytes % 16 != 0) return fail(DPF_ERR_PARAM, "dpf: bytes must be a multiple of 16");
+    if (bytes > 0 && !present(d_dbs, d_other)) return null_buffer();
+    if (!aligned(16, d_dbs, d_other)) return misaligned_buffer();
+    if (bytes == 0) return DPF_OK;
+    DeviceGuard g(device);
+    HIP_TRY(dpfk::launch_xor_words(d_dbs, d_other, bytes, (hipStream_t)stream));
     return DPF_OK;
 }
 

@@ -1,13 +1,17 @@
 // capi_pir_db.hip — the resident PIR database of the C ABI (include/dpf_hip.h):
 // a handle that keeps a DB sharded over the opened devices and answers,
-// updates, reads and privately writes it from host buffers.  Every shard runs
+// updates, reads, privately writes, exports, merges and clears it from host
+// buffers.  Every shard runs
 // the device-resident forms of capi_pir.hip on its device's stream under the
 // device's mutex; pir_update_plan.hpp has the shards' record ranges and the
 // planners of update / read that must agree with them.  No kernel is defined here.
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "capi_common.hpp"
+#include "pir_export_plan.hpp"
 #include "pir_update_plan.hpp"
 
 using namespace dpfc;
@@ -348,6 +352,78 @@ int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const uint8_
     return DPF_OK;
 }
 
+// ---- whole-DB read-out, merge and clear ---------------------------------------
+// dpf_set_export_limits: bytes of a piece's staging buffer (0: kPirUploadChunk).
+std::atomic<size_t> g_export_chunk{0};
+
+// The pieces of [first, first + n) (pir_export_plan.hpp), planned before
+// anything runs: a range outside the DB changes nothing.
+int plan_range(PirDb* h, uint64_t first, uint64_t n, std::vector<dpfh::ExportPiece>* pieces) {
+    const size_t lim = g_export_chunk.load(std::memory_order_relaxed);
+    const dpfh::ExportKind kind = h->grouped  ? dpfh::ExportKind::Grouped
+                                  : h->sparse ? dpfh::ExportKind::Sparse
+                                              : dpfh::ExportKind::Dense;
+    if (!dpfh::plan_export(kind, first, n, (lim ? lim : kPirUploadChunk) / h->w4, h->ranges, h->shard.size(), h->ngroups,
+                           h->gnrec, pieces))
+        return fail(DPF_ERR_PARAM, "dpf: record range outside the DB");
+    return DPF_OK;
+}
+
+// One piece under its device's mutex, on its stream, drained before the next:
+// a concurrent call sees the shard before or after the piece.  Export: the
+// piece un-sliced into staging, its wanted rows copied down.  Merge: the
+// wanted rows up into a zeroed piece (zero rows around them, zero pad bytes),
+// sliced into a second staging buffer and XORed into the shard, whose padding
+// therefore stays zero.  Row-major shards take plain copies and a plain XOR.
+int export_piece(PirDb* h, const dpfh::ExportPiece& p, uint8_t* out, const uint8_t* recs) {
+    const size_t rb = h->rec_bytes, w4 = h->w4;
+    Dev& d = *h->devs[p.shard];
+    uint8_t* db = (uint8_t*)h->shard[p.shard];
+    std::lock_guard<std::mutex> lk(d.mu);
+    DeviceGuard gd(d.id);
+    if (!h->sliced) {   // (w4 == rb, a multiple of 32)
+        uint8_t* rows = db + (p.local0 + p.skip) * rb;
+        if (out) {
+            HIP_TRY(hipMemcpyAsync(out + p.out * rb, rows, p.take * rb, hipMemcpyDeviceToHost, d.st));
+        } else {
+            HIP_TRY(d.out.ensure(p.take * rb));
+            HIP_TRY(hipMemcpyAsync(d.out.p, recs + p.out * rb, p.take * rb, hipMemcpyHostToDevice, d.st));
+            HIP_TRY(dpfk::launch_xor_words(rows, (const uint8_t*)d.out.p, p.take * rb, d.st));
+        }
+    } else {
+        uint8_t* part = db + p.local0 * w4;
+        HIP_TRY(d.out.ensure(p.nrec * w4));
+        uint8_t* stage = (uint8_t*)d.out.p;
+        if (out) {
+            HIP_TRY(dpfk::launch_unslice_db(part, p.nrec, w4, stage, d.st));
+            HIP_TRY(copy_rows_down(out + p.out * rb, stage + p.skip * w4, w4, rb, p.take, d.st));
+        } else {
+            const size_t sliced = dpfk::pir_sliced_bytes(p.nrec, w4);
+            HIP_TRY(d.work.ensure(sliced));
+            HIP_TRY(hipMemsetAsync(stage, 0, p.nrec * w4, d.st));
+            HIP_TRY(copy_rows_up(stage + p.skip * w4, w4, recs + p.out * rb, rb, p.take, d.st));
+            HIP_TRY(dpfk::launch_slice_db(stage, p.nrec, w4, (uint8_t*)d.work.p, d.st));
+            HIP_TRY(dpfk::launch_xor_words(part, (const uint8_t*)d.work.p, sliced, d.st));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(d.st));
+    if (d.out.cap > 2 * kStageBytes) d.out.release();   // a large piece's staging is not kept
+    if (!out && d.work.cap > 2 * kStageBytes) d.work.release();
+    return DPF_OK;
+}
+
+int pir_export_or_xor(void* handle, uint64_t first, uint64_t n, uint8_t* out, const uint8_t* recs) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    std::vector<dpfh::ExportPiece> pieces;
+    if (int rc = plan_range(h, first, n, &pieces)) return rc;
+    if (n == 0) return DPF_OK;
+    if (!out && !recs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    for (const dpfh::ExportPiece& p : pieces)
+        if (int rc = export_piece(h, p, out, recs)) return rc;
+    return DPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -428,6 +504,34 @@ int dpf_pir_db_update(void* handle, const uint64_t* idx, const uint8_t* recs, si
 }
 int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out) {
     return pir_update_or_read(handle, idx, n, nullptr, out);
+}
+
+int dpf_pir_db_export(void* handle, uint64_t first, uint64_t n, uint8_t* out) {
+    return pir_export_or_xor(handle, first, n, out, nullptr);
+}
+int dpf_pir_db_xor_records(void* handle, uint64_t first, uint64_t n, const uint8_t* recs) {
+    return pir_export_or_xor(handle, first, n, nullptr, recs);
+}
+
+// Every shard zeroed on its stream under its device's mutex; a sparse handle keeps its points.
+int dpf_pir_db_clear(void* handle) {
+    PirDb* h = (PirDb*)handle;
+    if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
+    for (size_t s = 0; s < h->shard.size(); ++s) {
+        Dev& d = *h->devs[s];
+        std::lock_guard<std::mutex> lk(d.mu);
+        DeviceGuard gd(d.id);
+        const size_t bytes = h->sliced ? (size_t)dpfk::pir_sliced_bytes(h->shard_n[s], h->w4) : h->shard_n[s] * h->w4;
+        if (bytes == 0) continue;
+        HIP_TRY(hipMemsetAsync(h->shard[s], 0, bytes, d.st));
+        HIP_TRY(hipStreamSynchronize(d.st));
+    }
+    return DPF_OK;
+}
+
+int dpf_set_export_limits(size_t chunk_bytes) {
+    g_export_chunk.store(chunk_bytes);
+    return DPF_OK;
 }
 
 // Every shard applies the batch to its slice: keys and messages up through

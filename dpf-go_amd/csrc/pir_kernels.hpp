@@ -91,6 +91,17 @@ hipError_t launch_update_rows(uint8_t* db, uint64_t nrec, uint64_t rec_bytes, co
 hipError_t launch_gather_rows(const uint8_t* db, uint64_t nrec, uint64_t rec_bytes, const uint64_t* idx, uint64_t n,
                               uint8_t* out, hipStream_t st);
 
+// The whole-DB read-out (pir_unslice.hip).  launch_unslice_db is the inverse
+// of launch_slice_db: db [nrec][rec_bytes] row-major from the sliced layout of
+// any width; exactly nrec rows are written, whatever the rows past nrec of the
+// last super-group hold.  As for slicing, records [256 S0, ...) come from
+// dbs + S0 * 256 * rec_bytes.  launch_xor_words: dst ^= src over `bytes` (a
+// multiple of 16), the merge of two sliced buffers of one shape (or of plain
+// rows).  No workspace, asynchronous on st; all pointers 16-byte aligned.
+constexpr uint64_t kXorWordsMaxBlocks = 8192;   // grid-stride beyond: 8 workgroups for each of 4 SIMDs of 256 CUs
+hipError_t launch_unslice_db(const uint8_t* dbs, uint64_t nrec, uint64_t rec_bytes, uint8_t* db, hipStream_t st);
+hipError_t launch_xor_words(uint8_t* dst, const uint8_t* src, uint64_t bytes, hipStream_t st);
+
 // Private writes, the dual of the fold (k_scatter_sliced; k_xor_scatter_rows
 // on a row-major DB): record i ^= XOR over keys k < nkeys with bit i of
 // bits[k * words_per_key ...] set of msgs[k * rec_bytes ..), for i < nrec.

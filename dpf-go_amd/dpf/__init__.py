@@ -121,6 +121,13 @@ SIGNATURES = {
     "dpf_pir_write_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_write_grouped": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_scatter_grouped_form_for": (_int, [_u64, _u64, _u64, _sz, _int, ctypes.POINTER(ScatterGroupedFormC)]),
+    "dpf_pir_db_unslice_any_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_unslice_grouped_dev": (_int, [_int, _vp, _u64, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_xor_sliced_dev": (_int, [_int, _vp, _vp, _sz, _vp]),
+    "dpf_pir_db_export": (_int, [_vp, _u64, _u64, _u8p]),
+    "dpf_pir_db_xor_records": (_int, [_vp, _u64, _u64, _u8p]),
+    "dpf_pir_db_clear": (_int, [_vp]),
+    "dpf_set_export_limits": (_int, [_sz]),
     "dpf_expand_keys_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp]),
     "dpf_evalfull_expanded_dev": (_int, [_int, _vp, _sz, _u32, _u32, _u64, _vp, _vp]),
     "dpf_forget_workspace": (_int, [_vp]),
@@ -883,6 +890,33 @@ def scatter_grouped_form_for(ngroups: int, keys_per_group: int, nrec: int, rec_b
     return ScatterGroupedForm(*[int(getattr(c, f)) for f in ScatterGroupedForm._fields])
 
 
+# ---- whole-DB read-out: un-slice, XOR-merge ----
+def pir_db_unslice_any_dev(d_dbs, nrec: int, rec_bytes: int, d_db, device: int = 0, stream=None) -> None:
+    """The inverse of pir_db_slice_any_dev: d_db [nrec][rec_bytes] row-major from
+    the sliced layout; exactly nrec rows are written."""
+    _check(lib().dpf_pir_db_unslice_any_dev(device, _ptr(d_dbs), nrec, rec_bytes, _ptr(d_db), _stream_handle(stream)))
+
+
+def pir_db_unslice_grouped_dev(d_dbs, ngroups: int, nrec: int, rec_bytes: int, d_db, device: int = 0,
+                               stream=None) -> None:
+    """The inverse of pir_db_slice_grouped_dev: d_db [ngroups][nrec][rec_bytes],
+    tight, from the grouped layout; the padding behind each group is not written."""
+    _check(lib().dpf_pir_db_unslice_grouped_dev(device, _ptr(d_dbs), ngroups, nrec, rec_bytes, _ptr(d_db),
+                                                _stream_handle(stream)))
+
+
+def pir_db_xor_sliced_dev(d_dbs, d_other, nbytes: int, device: int = 0, stream=None) -> None:
+    """d_dbs ^= d_other over nbytes (a multiple of 16): two sliced buffers of one shape merged."""
+    _check(lib().dpf_pir_db_xor_sliced_dev(device, _ptr(d_dbs), _ptr(d_other), nbytes, _stream_handle(stream)))
+
+
+def set_export_limits(chunk_bytes: int = 0) -> None:
+    """Tuning / test limit of the staging bytes of one piece of PirDB.export /
+    xor_records (0 = default, 256 MiB; dpf_set_export_limits).  Results do not
+    depend on it."""
+    _check(lib().dpf_set_export_limits(chunk_bytes))
+
+
 def set_fold_limits(max_blocks: int = 0, max_sg_per_block: int = 0) -> None:
     """Tuning / test limits of the fold launches (0 = default): workgroups per
     launch, and super-groups (256 records) per matrix-core fold workgroup;
@@ -1006,6 +1040,32 @@ class PirDB:
         out = np.zeros((ix.size, self.rec_bytes), np.uint8)
         _check(lib().dpf_pir_db_read(self._h, ix.ctypes.data_as(_u64p), ix.size, _buf(out)))
         return out
+
+    def export(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The records [first, first + n) as the DB now holds them, (n, rec_bytes);
+        n=None: up to the end.  The whole-DB read-out: no index list, pieces
+        of whole super-groups un-sliced on the device.  A range outside the DB
+        raises DPFPanic (DPF_ERR_PARAM)."""
+        if first < 0 or (n is not None and n < 0):
+            raise ValueError("first and n must not be negative")
+        if n is None:
+            n = max(0, self.nrec - first)
+        out = np.zeros((n, self.rec_bytes), np.uint8)
+        _check(lib().dpf_pir_db_export(self._h, first, n, _buf(out)))
+        return out
+
+    def xor_records(self, recs, first: int = 0) -> None:
+        """Record first + i ^= recs[i]: the other server's exported share merged
+        into this one.  A range outside the DB raises DPFPanic and changes
+        nothing."""
+        r = np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1)
+        if first < 0 or r.size % self.rec_bytes:
+            raise ValueError("recs must hold whole records of %d bytes, first must not be negative" % self.rec_bytes)
+        _check(lib().dpf_pir_db_xor_records(self._h, first, r.size // self.rec_bytes, _buf(r)))
+
+    def clear(self) -> None:
+        """Every record := 0 (the next epoch's empty table); a sparse handle keeps its points."""
+        _check(lib().dpf_pir_db_clear(self._h))
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -800,6 +800,64 @@ typedef struct dpf_scatter_grouped_form {
 int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
                                  dpf_scatter_grouped_form* form);
 
+/* ---- Whole-DB read-out of a resident DB: un-slice, XOR-merge, clear -------
+ * A DB that accumulates private writes (a mailbox, a bulletin board) is read
+ * out whole at the end of an epoch: each server exports its share, the shares
+ * are XORed, and the table is cleared for the next epoch.
+ * dpf_pir_db_unslice_any_dev is the inverse of dpf_pir_db_slice_any_dev: d_db
+ * [nrec][rec_bytes], row-major and tightly packed, from the any-width sliced
+ * layout d_dbs (k_unslice_db: the tiles of up to 4 columns by coalesced 16-byte
+ * loads through LDS, a five-step 32 x 32 bit transposition per tile, rows of
+ * more than 32 bytes stored through LDS so that consecutive lanes write
+ * consecutive bytes).  Exactly nrec * rec_bytes bytes are written: rows
+ * past nrec of the last super-group are neither written nor, whatever d_dbs
+ * holds there, read into a written row.  As for slicing, a range of whole
+ * super-groups is un-sliced by offsetting both pointers: records
+ * [256*S0, 256*S0 + n) come from d_dbs + S0*256*rec_bytes into
+ * d_db + S0*256*rec_bytes (pass n as nrec).
+ * dpf_pir_db_unslice_grouped_dev is the inverse of dpf_pir_db_slice_grouped_dev:
+ * d_db [ngroups][nrec][rec_bytes], tight; the zero records behind each group's
+ * nrec are not written (one launch per group where groups have padding).
+ * dpf_pir_db_xor_sliced_dev: d_dbs ^= d_other over `bytes` bytes, the merge of
+ * two sliced (or grouped, or row-major) buffers of one shape; zero padding
+ * stays zero.
+ * Checked before any device call, in this order: rec_bytes (a positive
+ * multiple of 4, at most DPF_PIR_MAX_REC_BYTES) resp. bytes (a multiple of
+ * 16); the products of the sizes not fitting 64 bits; a null buffer where
+ * there is work; a buffer that is not 16-byte aligned.  All DPF_ERR_PARAM.
+ * Nothing to do (nrec == 0, ngroups == 0, bytes == 0) then returns DPF_OK
+ * without a launch.  All three are asynchronous on `stream` and can be
+ * captured: no synchronisation, no allocation, no memset, no workspace. */
+int dpf_pir_db_unslice_any_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_db,
+                               void* stream);
+int dpf_pir_db_unslice_grouped_dev(int device, const uint8_t* d_dbs, uint64_t ngroups, uint64_t nrec,
+                                   size_t rec_bytes, uint8_t* d_db, void* stream);
+int dpf_pir_db_xor_sliced_dev(int device, uint8_t* d_dbs, const uint8_t* d_other, size_t bytes, void* stream);
+/* The same on a handle of any kind (dense, sparse, grouped; any shard count;
+ * sliced or, with DPF_PIR_FOLD=lds, row-major shards), over the records
+ * [first, first + n) of the handle's index space (a sparse handle: positions
+ * in its list; a grouped one: g * nrec + i, the padding behind a group is
+ * never delivered).  A range that leaves [0, dpf_pir_db_nrec) -- first + n
+ * overflowing included -- is DPF_ERR_PARAM and nothing is changed; n == 0 is
+ * DPF_OK; a NULL handle or, with n > 0, a NULL buffer is DPF_ERR_PARAM.
+ * dpf_pir_db_export: out [n][dpf_pir_db_rec_bytes(handle)], tight := the
+ * records.  dpf_pir_db_xor_records: record first + i ^= recs[i], rows of the
+ * same width; the pad bytes and pad records of every shard and group stay
+ * zero.  Both walk the range in pieces of whole super-groups of one shard, at
+ * most dpf_set_export_limits' bytes each (csrc/pir_export_plan.hpp): a piece
+ * is un-sliced into a staging buffer and copied down, resp. staged, sliced and
+ * XORed into the shard, on its device's stream under that device's mutex, so a
+ * concurrent dpf_pir_answer sees a shard wholly before or wholly after each
+ * piece.  dpf_pir_db_clear: every record := 0 (one memset per shard, under the
+ * same mutex); a sparse handle keeps its points.  All synchronous.
+ * dpf_set_export_limits: tuning / test limit of a piece's staging bytes
+ * (process-wide; 0 = the default, 256 MiB; a piece is at least one
+ * super-group).  Results do not depend on it.  Returns 0. */
+int dpf_pir_db_export(void* handle, uint64_t first, uint64_t n, uint8_t* out);
+int dpf_pir_db_xor_records(void* handle, uint64_t first, uint64_t n, const uint8_t* recs);
+int dpf_pir_db_clear(void* handle);
+int dpf_set_export_limits(size_t chunk_bytes);
+
 #ifdef __cplusplus
 }
 #endif
