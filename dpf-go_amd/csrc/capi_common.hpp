@@ -220,9 +220,9 @@ inline SparseWs sparse_ws(void* d_work, size_t nkeys, uint64_t nrec, uint32_t lo
 // d_work of the grouped PIR composite: [tree workspace of all ngroups * kpg
 // keys | selection bits, a whole-domain EvalFull row of per_key bytes a key |
 // the grouped fold's scratch], the first two parts padded to 256 B.  The
-// grouped fold writes no scratch (dpfh::GroupedFoldPlan::scratch_bytes); its
+// grouped fold writes no scratch (dpfh::GroupedPlan::scratch_bytes); its
 // size function keeps the ABI's 16-byte minimum.
-inline size_t group_fold_ws_bytes() { return std::max<size_t>(16, dpfh::GroupedFoldPlan{}.scratch_bytes()); }
+inline size_t group_fold_ws_bytes() { return std::max<size_t>(16, dpfh::GroupedPlan{}.scratch_bytes()); }
 struct GroupWs {
     uint8_t* bits;
     uint64_t per_key;

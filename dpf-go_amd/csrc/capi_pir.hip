@@ -170,6 +170,40 @@ int pir_write(RecRule rule, bool sliced, int device, const uint8_t* d_keys, size
     return DPF_OK;
 }
 
+// The grouped slice (to_flat) / un-slice entries: width, the products, null,
+// alignment, empty; then `launch` once where the groups have no padding (the
+// row-major DB is the flat one), else per group at its row-major and flat
+// strides (the zero records behind its nrec: zero-filled / not written).
+template <class Launch>
+int grouped_reslice(Launch launch, bool to_flat, const char* too_large, int device, const uint8_t* d_src, uint64_t ngroups,
+                    uint64_t nrec, size_t rec_bytes, uint8_t* d_dst, void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    uint64_t bytes = 0;
+    if (!dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, too_large);
+    if (bytes > 0 && !present(d_src, d_dst)) return null_buffer();
+    if (!aligned(16, d_src, d_dst)) return misaligned_buffer();
+    if (bytes == 0) return DPF_OK;
+    DeviceGuard g(device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t gs = dpfh::group_stride(nrec);
+    if (gs == nrec) {
+        HIP_TRY(launch(d_src, ngroups * nrec, rec_bytes, d_dst, st));
+        return DPF_OK;
+    }
+    const uint64_t from = (to_flat ? nrec : gs) * rec_bytes, to = (to_flat ? gs : nrec) * rec_bytes;
+    for (uint64_t i = 0; i < ngroups; ++i) HIP_TRY(launch(d_src + i * from, nrec, rec_bytes, d_dst + i * to, st));
+    return DPF_OK;
+}
+
+// The two grouped composites' front: group_ws (the write leaves the fold's
+// scratch unused) and the tree pass of all keys into its selection rows.
+int group_tree(const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, void* d_work, hipStream_t st, GroupWs* w) {
+    const uint32_t stop = stop_of(logN);
+    *w = group_ws(d_work, nkeys, stop);
+    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, 0, 0, w->bits, w->per_key, d_work, st, want_bs()));
+    return DPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,58 +426,23 @@ size_t dpf_pir_db_grouped_size(uint64_t ngroups, uint64_t nrec, size_t rec_bytes
 
 int dpf_pir_db_slice_grouped_dev(int device, const uint8_t* d_db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes,
                                  uint8_t* d_dbs, void* stream) {
-    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
-    uint64_t bytes = 0;
-    if (!dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
-    if (bytes > 0 && !present(d_db, d_dbs)) return null_buffer();
-    if (!aligned(16, d_db, d_dbs)) return misaligned_buffer();
-    if (bytes == 0) return DPF_OK;
-    DeviceGuard g(device);
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t gs = dpfh::group_stride(nrec);
-    if (gs == nrec) {   // no padding: the row-major DB is the flat one
-        HIP_TRY(dpfk::launch_slice_db(d_db, ngroups * nrec, rec_bytes, d_dbs, st));
-        return DPF_OK;
-    }
-    for (uint64_t i = 0; i < ngroups; ++i)   // a group's last super-group is zero-filled behind its nrec records
-        HIP_TRY(dpfk::launch_slice_db(d_db + i * nrec * rec_bytes, nrec, rec_bytes, d_dbs + i * gs * rec_bytes, st));
-    return DPF_OK;
+    return grouped_reslice(dpfk::launch_slice_db, true, "dpf: grouped DB too large", device, d_db, ngroups, nrec, rec_bytes,
+                           d_dbs, stream);
 }
 
 // ---- the whole-DB read-out: un-slice, and the merge of two sliced buffers ----
-// The inverse of the two slice entries above, with their rules in their order:
-// width, the products, null, alignment.
+// The inverse of the two slice entries above, with their rules in their order
+// (grouped_reslice); a DB of any width is one group.
 int dpf_pir_db_unslice_any_dev(int device, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_db,
                                void* stream) {
-    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
-    uint64_t bytes = 0;
-    if (!dpfh::grouped_bytes(1, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: DB too large");
-    if (bytes > 0 && !present(d_dbs, d_db)) return null_buffer();
-    if (!aligned(16, d_dbs, d_db)) return misaligned_buffer();
-    if (bytes == 0) return DPF_OK;
-    DeviceGuard g(device);
-    HIP_TRY(dpfk::launch_unslice_db(d_dbs, nrec, rec_bytes, d_db, (hipStream_t)stream));
-    return DPF_OK;
+    return grouped_reslice(dpfk::launch_unslice_db, false, "dpf: DB too large", device, d_dbs, 1, nrec, rec_bytes, d_db,
+                           stream);
 }
 
 int dpf_pir_db_unslice_grouped_dev(int device, const uint8_t* d_dbs, uint64_t ngroups, uint64_t nrec, size_t rec_bytes,
                                    uint8_t* d_db, void* stream) {
-    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
-    uint64_t bytes = 0;
-    if (!dpfh::grouped_bytes(ngroups, nrec, rec_bytes, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
-    if (bytes > 0 && !present(d_dbs, d_db)) return null_buffer();
-    if (!aligned(16, d_dbs, d_db)) return misaligned_buffer();
-    if (bytes == 0) return DPF_OK;
-    DeviceGuard g(device);
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t gs = dpfh::group_stride(nrec);
-    if (gs == nrec) {   // no padding: the flat DB is the row-major one
-        HIP_TRY(dpfk::launch_unslice_db(d_dbs, ngroups * nrec, rec_bytes, d_db, st));
-        return DPF_OK;
-    }
-    for (uint64_t i = 0; i < ngroups; ++i)   // the zero records behind a group's nrec are not written
-        HIP_TRY(dpfk::launch_unslice_db(d_dbs + i * gs * rec_bytes, nrec, rec_bytes, d_db + i * nrec * rec_bytes, st));
-    return DPF_OK;
+    return grouped_reslice(dpfk::launch_unslice_db, false, "dpf: grouped DB too large", device, d_dbs, ngroups, nrec,
+                           rec_bytes, d_db, stream);
 }
 
 int dpf_pir_db_xor_sliced_dev(int device, uint8_t* d_dbs, const uint8_t* d_other, size_t bytes, void* stream) {
@@ -500,9 +499,8 @@ int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t klen, u
         HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
         return DPF_OK;
     }
-    const uint32_t stop = stop_of(logN);
-    const GroupWs w = group_ws(d_work, nkeys, stop);
-    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, 0, 0, w.bits, w.per_key, d_work, st, want_bs()));
+    GroupWs w;
+    if (int rc = group_tree(d_keys, klen, nkeys, logN, d_work, st, &w)) return rc;
     HIP_TRY(dpfk::launch_pir_fold_grouped((const uint32_t*)w.bits, w.per_key / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
                                           nrec, rec_bytes, (uint32_t*)d_ans, w.scratch, st));
     return DPF_OK;
@@ -540,9 +538,8 @@ int dpf_pir_write_grouped_dev(int device, const uint8_t* d_keys, size_t klen, ui
     DeviceGuard g(device);
     CuScope cus(stream);
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t stop = stop_of(logN);
-    const GroupWs w = group_ws(d_work, nkeys, stop);   // the answer's layout; the fold's scratch stays unused
-    HIP_TRY(tree_from_keys(d_keys, klen, nkeys, stop, 0, 0, w.bits, w.per_key, d_work, st, want_bs()));
+    GroupWs w;
+    if (int rc = group_tree(d_keys, klen, nkeys, logN, d_work, st, &w)) return rc;
     HIP_TRY(dpfk::launch_scatter_grouped((const uint32_t*)w.bits, w.per_key / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
                                          nrec, rec_bytes, d_msgs, st));
     return DPF_OK;
@@ -553,8 +550,8 @@ int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint
     if (form == nullptr || !rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK ||
         nrec > UINT64_MAX - 255)
         return fail(DPF_ERR_PARAM, "dpf: form query out of range");
-    const dpfh::GroupedScatterPlan p = dpfk::scatter_grouped_plan(ngroups, (uint32_t)keys_per_group, nrec, rec_bytes,
-                                                                  (uint64_t)(cus > 0 ? cus : 0));
+    const dpfh::GroupedPlan p =
+        dpfk::scatter_grouped_plan(ngroups, (uint32_t)keys_per_group, nrec, rec_bytes, (uint64_t)(cus > 0 ? cus : 0));
     memset(form, 0, sizeof *form);
     form->route = (uint32_t)p.route;
     form->columns = p.C;
@@ -565,7 +562,7 @@ int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint
     form->passes = p.passes();
     uint64_t launches = 0;
     uint32_t widths = 0;
-    p.for_each_launch([&](const dpfh::GroupScatterLaunch& l) {
+    p.for_each_launch([&](const dpfh::GroupLaunch& l) {
         ++launches;
         if (l.u0 == 0) widths |= 1u << (l.kp - 1);
         return 0;

@@ -265,6 +265,28 @@ int on_shard(PirDb* h, size_t s, const uint8_t* keys, size_t klen, size_t nkeys,
     return DPF_OK;
 }
 
+int check_grouped_nkeys(const PirDb* h, size_t nkeys) {
+    if (h->ngroups == 0 ? nkeys != 0 : nkeys % h->ngroups != 0)
+        return fail(DPF_ERR_PARAM, "dpf: nkeys must be a multiple of the handle's groups");
+    return DPF_OK;
+}
+
+// The key rows [ngroups][kpg] split over the shards' group ranges: shard s takes
+// its turn (on_shard) with the rows of its groups [g0, g0 + ng) and body(d, s,
+// g0, ng, kpg); one without groups, or with skip_empty without records, does not.
+template <class Body>
+int on_group_shards(PirDb* h, const uint8_t* keys, size_t klen, size_t nkeys, bool skip_empty, Body body) {
+    const int g = (int)h->shard.size();
+    const size_t kpg = nkeys / h->ngroups;
+    return shard((size_t)g, g, [&](int, size_t s, size_t) {
+        const uint64_t g0 = h->group_lo(s), ng = h->group_hi(s) - g0;
+        if (ng == 0 || (skip_empty && h->gnrec == 0)) return (int)DPF_OK;
+        const size_t nk = ng * kpg;
+        return on_shard(h, s, keys + g0 * kpg * klen, klen, nk, nk * klen, std::max<size_t>(32, nk * h->w4),
+                        [&](Dev& d) { return body(d, s, g0, ng, kpg); });
+    });
+}
+
 // The device form of shard s by its kind (sparse, sliced, row-major; the last
 // takes multiples of 32 bytes, the others any multiple of 4): the answers
 // into, or with `write` the messages from, d.out.
@@ -464,23 +486,16 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
     if (h->grouped) {
         // keys [ngroups][kpg]: every shard gets its groups' key rows and
         // writes its groups' answers into their place; nothing to XOR.
-        if (h->ngroups == 0 ? nkeys != 0 : nkeys % h->ngroups != 0)
-            return fail(DPF_ERR_PARAM, "dpf: nkeys must be a multiple of the handle's groups");
+        if (int rc = check_grouped_nkeys(h, nkeys)) return rc;
         if (nkeys == 0) return DPF_OK;
         if (!keys || !ans) return fail(DPF_ERR_PARAM, "dpf: null buffer");
-        const size_t kpg = nkeys / h->ngroups;
-        return shard((size_t)g, g, [&](int, size_t s, size_t) {
-            const uint64_t g0 = h->group_lo(s), ng = h->group_hi(s) - g0;
-            if (ng == 0) return (int)DPF_OK;
-            const size_t nk = ng * kpg;
-            return on_shard(h, s, keys + g0 * kpg * klen, klen, nk, nk * klen, std::max<size_t>(32, nk * w4), [&](Dev& d) {
-                if (int r = dpf_pir_answer_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
-                                                       (const uint8_t*)h->shard[s], h->gnrec, w4, (uint8_t*)d.out.p,
-                                                       d.work.p, d.st))
-                    return r;
-                HIP_TRY(copy_rows_down(ans + g0 * kpg * rb, d.out.p, w4, rb, nk, d.st));
-                return (int)DPF_OK;
-            });
+        return on_group_shards(h, keys, klen, nkeys, false, [&](Dev& d, size_t s, uint64_t g0, uint64_t ng, size_t kpg) {
+            if (int r = dpf_pir_answer_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
+                                                   (const uint8_t*)h->shard[s], h->gnrec, w4, (uint8_t*)d.out.p, d.work.p,
+                                                   d.st))
+                return r;
+            HIP_TRY(copy_rows_down(ans + g0 * kpg * rb, d.out.p, w4, rb, ng * kpg, d.st));
+            return (int)DPF_OK;
         });
     }
     std::vector<std::vector<uint8_t>> part((size_t)g, std::vector<uint8_t>(nkeys * rb));
@@ -562,21 +577,14 @@ int dpf_pir_db_write_grouped(void* handle, const uint8_t* keys, size_t klen, siz
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
     if (!h->grouped) return fail(DPF_ERR_PARAM, "dpf: dpf_pir_db_write_grouped takes a grouped handle only");
     if (int rc = check_key(klen, h->logN)) return rc;
-    if (h->ngroups == 0 ? nkeys != 0 : nkeys % h->ngroups != 0)
-        return fail(DPF_ERR_PARAM, "dpf: nkeys must be a multiple of the handle's groups");
+    if (int rc = check_grouped_nkeys(h, nkeys)) return rc;
     if (nkeys == 0) return DPF_OK;
     if (!keys || !msgs) return fail(DPF_ERR_PARAM, "dpf: null buffer");
-    const int g = (int)h->shard.size();
-    const size_t rb = h->rec_bytes, w4 = h->w4, kpg = nkeys / h->ngroups;
-    return shard((size_t)g, g, [&](int, size_t s, size_t) {
-        const uint64_t g0 = h->group_lo(s), ng = h->group_hi(s) - g0;
-        if (ng == 0 || h->gnrec == 0) return (int)DPF_OK;
-        const size_t nk = ng * kpg;
-        return on_shard(h, s, keys + g0 * kpg * klen, klen, nk, nk * klen, std::max<size_t>(32, nk * w4), [&](Dev& d) {
-            HIP_TRY(copy_rows_up(d.out.p, w4, msgs + g0 * kpg * rb, rb, nk, d.st));   // zero pad bytes: the DB's stay zero
-            return dpf_pir_write_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
-                                             (const uint8_t*)d.out.p, (uint8_t*)h->shard[s], h->gnrec, w4, d.work.p, d.st);
-        });
+    const size_t rb = h->rec_bytes, w4 = h->w4;
+    return on_group_shards(h, keys, klen, nkeys, true, [&](Dev& d, size_t s, uint64_t g0, uint64_t ng, size_t kpg) {
+        HIP_TRY(copy_rows_up(d.out.p, w4, msgs + g0 * kpg * rb, rb, ng * kpg, d.st));   // zero pad bytes: the DB's stay zero
+        return dpf_pir_write_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN, (const uint8_t*)d.out.p,
+                                         (uint8_t*)h->shard[s], h->gnrec, w4, d.work.p, d.st);
     });
 }
 

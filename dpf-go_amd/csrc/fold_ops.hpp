@@ -33,6 +33,12 @@ __device__ __forceinline__ uint4 x4(uint4 a, uint4 b) { return make_uint4(a.x ^ 
 __device__ __forceinline__ uint4 x4am(uint4 a, uint4 b, uint32_t m) {
     return make_uint4(xam(a.x, b.x, m), xam(a.y, b.y, m), xam(a.z, b.z, m), xam(a.w, b.w, m));
 }
+// The grouped kernels' tile address: the two uint4 of bit row `row` (of nrows)
+// in super-group S of group g, gsg super-groups a group (pir_group_plan.hpp's layout).
+template <class T>
+__device__ __forceinline__ T* group_tile(T* dbs, uint64_t g, uint64_t gsg, uint64_t S, uint32_t nrows, uint64_t row) {
+    return &dbs[((g * gsg + S) * nrows + row) * 2];
+}
 // Workgroup barrier of the folds' LDS staging: the plain barrier.  The
 // compiler keeps a global prefetch in flight across it; fencing the local
 // address space only measured identical (r05, profiles/r05/fold_barrier).

@@ -13,7 +13,7 @@
 namespace dpfk {
 
 // The popcount fold of k_fold_sliced_direct with a group coordinate.  Workgroup
-// x of the launch is unit u0 + x of the plan (dpfh::GroupedFoldPlan::unit): run
+// x of the launch is unit u0 + x of the plan (dpfh::group_unit): run
 // u % runs of column (u / runs) % C of group u / (runs * C), the group-local
 // super-groups [s0, s1) of that run.  Thread n of its 256 owns bit row n of the
 // column; per super-group it reads its 8 words once (the workgroup: 8 KiB
@@ -39,12 +39,9 @@ __global__ __launch_bounds__(256) void k_fold_grouped(const uint32_t* __restrict
                                                       uint64_t u0, uint32_t atomic) {
     const uint32_t n = threadIdx.x, l = n & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t u = u0 + blockIdx.x;
-    const uint64_t run = u % runs, t = u / runs;
-    const uint64_t g = t / C;
-    const uint32_t col = (uint32_t)(t % C);
-    const uint64_t s0 = run * spr;
-    const uint64_t s1 = s0 + spr < gsg ? s0 + spr : gsg;
+    const dpfh::GroupUnit un = dpfh::group_unit(u0 + blockIdx.x, runs, spr, gsg, C);
+    const uint64_t g = un.g, s0 = un.s0, s1 = un.s1;
+    const uint32_t col = un.c;
     const uint64_t key0 = g * kpg + k0;                         // first answer / selection row of this pass
     const uint32_t* sel = bits + key0 * wlim;
     uint32_t acc[KP];
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(256) void k_fold_grouped(const uint32_t* __restrict
         }
     };
     const uint64_t row = (uint64_t)col * 256 + n;
-    auto at = [&](uint64_t S) { return &dbs[((g * gsg + S) * nrows + row) * 2]; };
+    auto at = [&](uint64_t S) { return group_tile(dbs, g, gsg, S, nrows, row); };
     if (row < nrows) {
         uint64_t S = s0;
         for (; S + 1 < s1; S += 2) {
@@ -106,7 +103,7 @@ uint32_t group_kp_knob() {
 hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t ngroups,
                                    uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, uint32_t* ans,
                                    uint32_t* parts, hipStream_t st) {
-    (void)parts;   // the plan's launches write no scratch (dpfh::GroupedFoldPlan::scratch_bytes)
+    (void)parts;   // the plan's launches write no scratch (dpfh::GroupedPlan::scratch_bytes)
     if (!dpfh::rec_bytes_any_ok(rec_bytes)) return hipErrorInvalidValue;
     if (ngroups == 0 || keys_per_group == 0) return hipSuccess;
     if (ngroups * keys_per_group > UINT32_MAX) return hipErrorInvalidValue;
@@ -115,8 +112,8 @@ hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key,
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
     const uint64_t gsg = dpfh::group_stride(nrec) / 256;
     const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
-    const dpfh::GroupedFoldPlan p = dpfh::plan_fold_grouped(ngroups, gsg, C, keys_per_group, (uint64_t)cu_count(),
-                                                            fold_limits(), group_kp_knob());
+    const dpfh::GroupedPlan p =
+        dpfh::plan_fold_grouped(ngroups, gsg, C, keys_per_group, (uint64_t)cu_count(), fold_limits(), group_kp_knob());
     if (p.atomic())
         if (hipError_t e = launch_zero(ans, ans_bytes, st); e != hipSuccess) return e;
     return p.for_each_launch([&](const dpfh::GroupLaunch& l) {

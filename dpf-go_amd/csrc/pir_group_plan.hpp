@@ -1,7 +1,9 @@
 // pir_group_plan.hpp — grouped PIR: the layout rule of a grouped DB and the
-// launch plan of the grouped fold (k_fold_grouped, pir_fold_grouped.hip).
-// Host-only and header-only (no HIP), like pir_fold_plan.hpp, so
-// tests/c/pir_group_plan_test.cpp runs it under ASan/UBSan without a device.
+// launch plan of the grouped kernels (k_fold_grouped, pir_fold_grouped.hip;
+// k_scatter_grouped, pir_scatter_grouped.hip).
+// Header-only and plain C++ (no HIP), like pir_fold_plan.hpp, so
+// tests/c/pir_group_plan_test.cpp runs it under ASan/UBSan without a device;
+// under hipcc group_unit is device code as well.
 //
 // Layout.  A grouped DB is ngroups groups of nrec records, all of one shape.
 // On the device it is the any-width sliced layout of ONE flat DB in which
@@ -12,24 +14,35 @@
 // rec_bytes, and the slice / update / gather / scatter launchers work on it
 // by flat position.
 //
-// Plan.  A workgroup ("unit") folds one run of whole super-groups of one
-// column of one group for kp <= kGroupKeysPerPass keys of that group.  Units
-// are numbered run-fastest, then column, then group (GroupedFoldPlan::unit),
-// and a launch is a 1-D grid over a contiguous range of unit numbers: however
-// many groups there are, no grid dimension sees more than `cap` workgroups.
-// The keys of a group are taken in passes of 4, then 2, then 1 (one kernel
-// instantiation each); every pass walks all units.
-// What the plan guarantees, and no kernel can check:
-//   - every (group, super-group, column, key) cell is folded exactly once;
-//   - no run is empty and none crosses a group boundary (runs are cut inside
-//     [0, gsg) of their group);
+// Plan.  A workgroup ("unit") works on one run of whole super-groups of one
+// 32-byte column of one group for kp <= kGroupKeysPerPass keys of that group:
+// the fold XORs the selected words into the keys' answers, the scatter XORs the
+// keys' messages into the selected words.  Units are numbered run-fastest, then
+// column, then group (group_unit, the one decode of host and device), and a
+// launch is a 1-D grid over a contiguous range of unit numbers: however many
+// groups there are, no grid dimension sees more than `cap` workgroups, and few
+// large groups are cut into runs inside [0, gsg) of their group.  The keys of
+// a group are taken in passes (one kernel instantiation per width) in stream
+// order; every pass walks all units.  The fold and the scatter share this
+// GroupedPlan and differ in three rules, which are their builders'
+// (plan_fold_grouped here, plan_scatter_grouped in pir_group_scatter_plan.hpp):
+// how a group is cut into runs, the pass widths, and the route.
+// What a plan guarantees, and no kernel can check:
+//   - every (group, super-group, column, key) cell is worked on exactly once;
+//   - no run is empty and none crosses a group boundary;
+//   - the units of a pass are distinct (group, column, run) triples;
 //   - a launch has at most lim.max_blocks workgroups when dpf_set_fold_limits
 //     set fewer than its default, else at most kGroupMaxBlocks;
-//   - the launches write no scratch: with one run per group (runs == 1) every
-//     answer word has exactly one writer, which stores it; with more, the
-//     answers are cleared by a zero-fill launch earlier in stream order and every
-//     run XORs its words in with one vector atomic each (XOR is order-free,
-//     so the answers are deterministic).  scratch_bytes() is therefore 0.
+//   - the launches write no scratch: scratch_bytes() is 0.
+//   Fold only: with one run per group (runs == 1) every answer word has
+//     exactly one writer, which stores it; with more, the answers are cleared
+//     by a zero-fill launch earlier in stream order and every run XORs its
+//     words in with one vector atomic each (XOR is order-free, so the answers
+//     are deterministic): atomic().
+//   Scatter only: no run is longer than dpf_set_fold_limits' max_sg; within one
+//     launch (and within one pass) no two workgroups touch the same tile, and a
+//     pass reads and writes a tile at most once: no atomics; the pass widths
+//     sum to kpg.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -54,45 +67,73 @@ inline bool grouped_bytes(uint64_t ngroups, uint64_t nrec, uint64_t rec_bytes, u
 }
 
 // ---- the launch plan ---------------------------------------------------------
+#ifndef DPF_HD
+#if defined(__HIPCC__)
+#define DPF_HD __host__ __device__
+#else
+#define DPF_HD
+#endif
+#endif
+
 constexpr uint64_t kGroupMaxBlocks = 1ull << 20;   // workgroups per launch, the plan's own cap
-constexpr uint32_t kGroupKeysPerPass = 4;          // widest k_fold_grouped<KP>
+constexpr uint32_t kGroupKeysPerPass = 4;          // widest k_fold_grouped<KP> and k_scatter_grouped<KP>
 constexpr uint64_t kGroupPerCu = 8;                // workgroups per CU a pass aims at (k_fold_sliced_direct's)
+
+// How the grouped write runs (scatter_route, pir_group_scatter_plan.hpp); a fold is always grouped.
+enum GroupScatterRoute : uint32_t { kScatterRouteGrouped = 0, kScatterRouteLoop = 1 };
 
 // One launch: units [u0, u0 + blocks) for keys [k0, k0 + kp) of every group.
 struct GroupLaunch {
     uint64_t u0, blocks;
     uint32_t k0, kp;
 };
-// What a unit folds: super-groups [s0, s1) (group-local) of column c of group g.
+// What a unit works on: super-groups [s0, s1) (group-local) of column c of group g.
 struct GroupUnit {
     uint64_t g, s0, s1;
     uint32_t c;
 };
+// Unit u of a plan with `runs` runs of spr super-groups (the last what is left
+// of gsg) per (group, column) and C columns, on the host and in the kernels.
+DPF_HD inline GroupUnit group_unit(uint64_t u, uint64_t runs, uint64_t spr, uint64_t gsg, uint32_t C) {
+    const uint64_t r = u % runs, t = u / runs, g = t / C;
+    const uint32_t c = (uint32_t)(t % C);
+    const uint64_t s0 = r * spr;
+    return {g, s0, s0 + spr < gsg ? s0 + spr : gsg, c};
+}
 
-struct GroupedFoldPlan {
-    uint64_t ngroups, gsg;
-    uint32_t C, kpg;
-    uint64_t runs, spr;   // runs per (group, column), super-groups per run (the last run what is left)
-    uint64_t cap;         // workgroups per launch
-    uint32_t kp_max;      // keys per pass, a power of two <= kGroupKeysPerPass
+struct GroupedPlan {
+    uint64_t ngroups = 0, gsg = 0;
+    uint32_t C = 0, kpg = 0;
+    uint64_t runs = 1, spr = 1;   // runs per (group, column), super-groups per run (the last run what is left)
+    uint64_t cap = 1;             // workgroups per launch
+    uint32_t kp_max = kGroupKeysPerPass;   // widest key pass, a power of two
+    bool halve = false;   // fewer than kp_max keys left: widths halved until they fit (fold), else one pass of them (scatter)
+    GroupScatterRoute route = kScatterRouteGrouped;
 
-    uint64_t units() const { return ngroups * C * runs; }
-    // More than one run per group: cleared answers and atomic XORs (above).
+    uint64_t units() const { return kpg == 0 || gsg == 0 ? 0 : ngroups * C * runs; }
+    uint32_t pass_width(uint32_t left) const {
+        uint32_t kp = kp_max;
+        if (!halve) return left < kp ? left : kp;
+        while (kp > left) kp /= 2;
+        return kp;
+    }
+    uint64_t passes() const {
+        const uint32_t rest = kpg % kp_max;
+        return units() ? kpg / kp_max + (halve ? (uint64_t)__builtin_popcount(rest) : rest != 0) : 0;
+    }
+    GroupUnit unit(uint64_t u) const { return group_unit(u, runs, spr, gsg, C); }
+    // Fold: more than one run per group, so cleared answers and atomic XORs (above).
     bool atomic() const { return runs > 1; }
     size_t scratch_bytes() const { return 0; }
-    GroupUnit unit(uint64_t u) const {
-        const uint64_t r = u % runs, t = u / runs, s0 = r * spr;
-        return {t / C, s0, s0 + spr < gsg ? s0 + spr : gsg, (uint32_t)(t % C)};
-    }
 
-    // fn(const GroupLaunch&) for every launch in stream order, until one
-    // returns a nonzero (error) value, which is returned.
+    // fn(const GroupLaunch&) for every launch of the grouped route in stream
+    // order, until one returns a nonzero (error) value, which is returned.
     template <class F>
     auto for_each_launch(F fn) const -> decltype(fn(GroupLaunch{})) {
         const uint64_t n = units();
+        if (n == 0) return {};
         for (uint32_t k0 = 0; k0 < kpg;) {
-            uint32_t kp = kp_max;
-            while (kp > kpg - k0) kp /= 2;
+            const uint32_t kp = pass_width(kpg - k0);
             for (uint64_t u0 = 0; u0 < n; u0 += cap)
                 if (auto e = fn(GroupLaunch{u0, n - u0 < cap ? n - u0 : cap, k0, kp}); e != decltype(e){}) return e;
             k0 += kp;
@@ -101,22 +142,36 @@ struct GroupedFoldPlan {
     }
 };
 
-// ngroups groups of gsg super-groups and C columns, kpg keys per group, on
-// `cus` CUs.  Few large groups split into runs of whole pairs of super-groups
-// until a pass has about cus * kGroupPerCu workgroups (plan_fold_sliced_direct's
-// aim for its one DB); from ngroups * C workgroups upwards a group is one run.
+// What both builders start from: the shape and the workgroup cap (lim: clamp_fold_limits').
+inline GroupedPlan grouped_plan_shape(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg, FoldLimits lim) {
+    GroupedPlan p;
+    p.ngroups = ngroups, p.gsg = gsg, p.C = C, p.kpg = kpg;
+    p.cap = lim.max_blocks != 0 && lim.max_blocks < kFoldMaxBlocks ? lim.max_blocks : kGroupMaxBlocks;
+    return p;
+}
+// The runs per (group, column) a builder aims at (gsg > 0): few large groups
+// split until a pass has about cus * kGroupPerCu workgroups
+// (plan_fold_sliced_direct's aim); from that many (group, column) pairs, one run.
+inline uint64_t grouped_want_runs(uint64_t ngroups, uint64_t gsg, uint32_t C, uint64_t cus) {
+    const uint64_t cells = ngroups * C, aim = (cus ? cus : 1) * kGroupPerCu;
+    const uint64_t want = cells ? (aim + cells - 1) / cells : 1;
+    return want > gsg ? gsg : want;
+}
+
+// The grouped fold of ngroups groups of gsg super-groups and C columns, kpg
+// keys per group, on `cus` CUs.  Runs are whole pairs of super-groups
+// (lim.max_sg does not apply); the passes are 4, then 2, then 1 keys wide.
 // kp_max: the widest key pass (measurement knob; 0 or more than
 // kGroupKeysPerPass: that).
-inline GroupedFoldPlan plan_fold_grouped(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg, uint64_t cus,
-                                         FoldLimits lim, uint32_t kp_max = 0) {
-    const uint64_t cells = ngroups * C, aim = (cus ? cus : 1) * kGroupPerCu;
-    uint64_t want = cells ? (aim + cells - 1) / cells : 1;
-    if (want > gsg) want = gsg;
-    if (want < 1) want = 1;
-    const ChunkSplit s = gsg ? split_chunks(gsg, want, 2, gsg) : ChunkSplit{0, 1};
-    const uint64_t cap = lim.max_blocks != 0 && lim.max_blocks < kFoldMaxBlocks ? lim.max_blocks : kGroupMaxBlocks;
-    const uint32_t kp = kp_max >= 4 || kp_max == 0 ? 4u : kp_max >= 2 ? 2u : 1u;
-    return {ngroups, gsg, C, kpg, s.blocks, s.cpb, cap, kp};
+inline GroupedPlan plan_fold_grouped(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg, uint64_t cus,
+                                     FoldLimits lim, uint32_t kp_max = 0) {
+    GroupedPlan p = grouped_plan_shape(ngroups, gsg, C, kpg, lim);
+    p.halve = true;
+    p.kp_max = kp_max >= 4 || kp_max == 0 ? 4u : kp_max >= 2 ? 2u : 1u;
+    if (gsg == 0) return p;
+    const ChunkSplit s = split_chunks(gsg, grouped_want_runs(ngroups, gsg, C, cus), 2, gsg);
+    p.runs = s.blocks, p.spr = s.cpb;
+    return p;
 }
 
 // ---- the handle's shards and its update split ----------------------------------

@@ -3,7 +3,7 @@
 // the general-payload streaming consumer of EvalFull output; for the resident
 // DB's in-place updates; and for the fold's dual, the private write (messages
 // XORed into the selected records), both in pir_db_ops.hip.  How each launcher
-// sizes its launches: pir_fold_plan.hpp.
+// sizes its launches: pir_fold_plan.hpp; the grouped ones: pir_group_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,8 +124,9 @@ hipError_t launch_scatter_rows(const uint32_t* bits, uint64_t words_per_key, uin
 //   msgs[(g * keys_per_group + k) * rec_bytes ..).
 // Bits at positions >= nrec are ignored, so the zero records behind every
 // group's nrec stay zero; words past a row's end are not read.  Planned by
-// pir_group_scatter_plan.hpp under set_fold_limits' max_blocks and max_sg:
-// key passes of 4 and a last one of 1 to 3 over one grid of all groups, or (the plan's route
+// plan_scatter_grouped (pir_group_scatter_plan.hpp; the fold's plan type,
+// dpfh::GroupedPlan) under set_fold_limits' max_blocks and max_sg: key passes
+// of 4 and a last one of 1 to 3 over one grid of all groups, or (the plan's route
 // rule; few large groups with many keys) a loop of launch_scatter_sliced over
 // each group's flat range.  No workspace, no atomics, asynchronous on st.
 // bits, dbs and msgs 16-byte aligned; words_per_key a multiple of 4 covering
@@ -135,8 +136,8 @@ hipError_t launch_scatter_grouped(const uint32_t* bits, uint64_t words_per_key, 
                                   hipStream_t st);
 // The plan that call walks: under the current limits, on `cus` CUs (0: the
 // calling thread's budget), its route after the DPF_GROUP_SCATTER_ROUTE knob.
-dpfh::GroupedScatterPlan scatter_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec,
-                                              uint64_t rec_bytes, uint64_t cus);
+dpfh::GroupedPlan scatter_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes,
+                                       uint64_t cus);
 
 // Tuning / test limits of the fold launches: at most max_blocks workgroups
 // per launch (0 = the default, 1024), and at most max_sg super-groups per

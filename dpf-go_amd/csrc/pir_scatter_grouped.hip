@@ -1,8 +1,8 @@
 // pir_scatter_grouped.hip — the grouped private write: one scatter launch
 // rewrites many small DBs (groups), each under its own keys.  The dual of
-// pir_fold_grouped.hip; the layout rule is pir_group_plan.hpp's, the launch
-// plan and the route rule are in pir_group_scatter_plan.hpp, and the launcher
-// walks the plan.
+// pir_fold_grouped.hip; the layout rule and the launch plan are
+// pir_group_plan.hpp's, the plan's builder and the route rule are in
+// pir_group_scatter_plan.hpp, and the launcher walks the plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -22,7 +22,7 @@ __device__ __forceinline__ uint32_t group_live(uint64_t ww, uint64_t nrec) {
 }
 
 // The mirror of k_fold_grouped.  Workgroup x of the launch is unit u0 + x of
-// the plan (dpfh::GroupedScatterPlan::unit): run u % runs of column
+// the plan (dpfh::group_unit): run u % runs of column
 // (u / runs) % C of group u / (runs * C), the group-local super-groups
 // [s0, s1) of that run.  Thread n of its 256 owns bit row n of the column: per
 // super-group it loads its 8 words (two 16-byte loads; the workgroup: 8 KiB
@@ -51,12 +51,9 @@ __global__ __launch_bounds__(256) void k_scatter_grouped(const uint32_t* __restr
                                                          uint32_t nrows, const uint32_t* __restrict__ msgs,
                                                          uint32_t ntiles, uint64_t u0) {
     const uint32_t n = threadIdx.x;
-    const uint64_t u = u0 + blockIdx.x;
-    const uint64_t run = u % runs, t = u / runs;
-    const uint64_t g = t / C;
-    const uint32_t col = (uint32_t)(t % C);
-    const uint64_t s0 = run * spr;
-    const uint64_t s1 = s0 + spr < gsg ? s0 + spr : gsg;
+    const dpfh::GroupUnit un = dpfh::group_unit(u0 + blockIdx.x, runs, spr, gsg, C);
+    const uint64_t g = un.g, s0 = un.s0, s1 = un.s1;
+    const uint32_t col = un.c;
     const uint64_t key0 = g * kpg + k0;                         // first message / selection row of this pass
     const uint32_t* sel = bits + key0 * wlim;
     const uint32_t row = col * 256 + n;
@@ -65,7 +62,7 @@ __global__ __launch_bounds__(256) void k_scatter_grouped(const uint32_t* __restr
 #pragma unroll
     for (int j = 0; j < KP; ++j)
         m[j] = 0u - ((msgs[(key0 + j) * ntiles + (row >> 5)] >> (row & 31)) & 1u);
-    auto at = [&](uint64_t S) { return &dbs[((g * gsg + S) * nrows + row) * 2]; };
+    auto at = [&](uint64_t S) { return group_tile(dbs, g, gsg, S, nrows, row); };
     auto apply = [&](uint64_t S, uint4& a, uint4& b) __attribute__((always_inline)) {
         uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         if (8 * S + 8 <= wlim && (8 * S + 8) * 32 <= nrec) {     // uniform: whole words of live records
@@ -114,9 +111,9 @@ int route_knob() {
 
 }  // namespace
 
-dpfh::GroupedScatterPlan scatter_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec,
-                                              uint64_t rec_bytes, uint64_t cus) {
-    dpfh::GroupedScatterPlan p =
+dpfh::GroupedPlan scatter_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes,
+                                       uint64_t cus) {
+    dpfh::GroupedPlan p =
         dpfh::plan_scatter_grouped(ngroups, dpfh::group_stride(nrec) / 256, dpfh::rec_cols(rec_bytes), keys_per_group,
                                    cus ? cus : (uint64_t)cu_count(), fold_limits());
     if (const int knob = route_knob(); knob >= 0) p.route = (dpfh::GroupScatterRoute)knob;
@@ -132,7 +129,7 @@ hipError_t launch_scatter_grouped(const uint32_t* bits, uint64_t words_per_key, 
     if (ngroups * keys_per_group > UINT32_MAX) return hipErrorInvalidValue;
     const uint64_t gs = dpfh::group_stride(nrec);
     const uint32_t T = dpfh::rec_tiles(rec_bytes);
-    const dpfh::GroupedScatterPlan p = scatter_grouped_plan(ngroups, keys_per_group, nrec, rec_bytes, 0);
+    const dpfh::GroupedPlan p = scatter_grouped_plan(ngroups, keys_per_group, nrec, rec_bytes, 0);
     if (p.route == dpfh::kScatterRouteLoop) {
         // Group g is the flat records [g * gs, g * gs + nrec): a sliced DB of its own.
         for (uint64_t g = 0; g < ngroups; ++g)
@@ -143,7 +140,7 @@ hipError_t launch_scatter_grouped(const uint32_t* bits, uint64_t words_per_key, 
                 return e;
         return hipSuccess;
     }
-    return p.for_each_launch([&](const dpfh::GroupScatterLaunch& l) {
+    return p.for_each_launch([&](const dpfh::GroupLaunch& l) {
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3((uint32_t)l.blocks), dim3(256), 0, st, bits, words_per_key,
                                reinterpret_cast<uint4*>(dbs), nrec, p.gsg, p.C, p.runs, p.spr, p.kpg, l.k0,

@@ -41,12 +41,13 @@ constexpr uint64_t kGridX = (1ull << 31) - 1;   // HIP's bound on gridDim.x
 static void check_plan(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg, uint64_t cus, uint32_t max_blocks) {
 #define AT "ngroups=%llu gsg=%llu C=%u kpg=%u cus=%llu max_blocks=%u", (ull)ngroups, (ull)gsg, C, kpg, (ull)cus, max_blocks
     const FoldLimits lim = clamp_fold_limits(max_blocks, 0);
-    const GroupedFoldPlan p = plan_fold_grouped(ngroups, gsg, C, kpg, cus, lim);
+    const GroupedPlan p = plan_fold_grouped(ngroups, gsg, C, kpg, cus, lim);
     ++g_plans;
     const uint64_t cap = max_blocks ? max_blocks : kGroupMaxBlocks;
     CHECK(p.cap == cap && p.cap <= kGridX, AT);
     CHECK(p.runs >= 1 && p.runs <= gsg && p.spr >= 1, AT);
     CHECK((p.runs - 1) * p.spr < gsg && p.runs * p.spr >= gsg, AT);   // no empty run, the runs reach gsg
+    CHECK(p.route == kScatterRouteGrouped, AT);                       // a fold has no other route
     CHECK(p.scratch_bytes() == 0, AT);                                // what the size function promises: none
     // Few large groups split into runs of whole pairs; groups enough to fill the chip do not.
     if (2 * ngroups * C <= cus * kGroupPerCu && gsg >= 3) CHECK(p.runs > 1, AT);
@@ -73,7 +74,8 @@ static void check_plan(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg,
         CHECK(l.u0 + l.blocks <= p.units(), AT);
         u_at = l.u0 + l.blocks;
         for (uint64_t u = l.u0; u < l.u0 + l.blocks && g_fail == 0; ++u) {
-            const GroupUnit x = p.unit(u);
+            const GroupUnit x = p.unit(u), d = group_unit(u, p.runs, p.spr, p.gsg, p.C);
+            CHECK(x.g == d.g && x.s0 == d.s0 && x.s1 == d.s1 && x.c == d.c, AT);   // the kernels' decode
             CHECK(x.g < ngroups && x.c < C, AT);
             CHECK(x.s0 < x.s1 && x.s1 <= gsg, AT);          // not empty, inside its group
             if (!(x.g < ngroups && x.c < C && x.s0 < x.s1 && x.s1 <= gsg)) return 0;

@@ -45,13 +45,13 @@ static void check_plan(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg,
                        uint32_t max_sg) {
 #define AT "ngroups=%llu gsg=%llu C=%u kpg=%u cus=%llu max_blocks=%u max_sg=%u", (ull)ngroups, (ull)gsg, C, kpg, (ull)cus, max_blocks, max_sg
     const FoldLimits lim = clamp_fold_limits(max_blocks, max_sg);
-    const GroupedScatterPlan p = plan_scatter_grouped(ngroups, gsg, C, kpg, cus, lim);
+    const GroupedPlan p = plan_scatter_grouped(ngroups, gsg, C, kpg, cus, lim);
     ++g_plans;
     const uint64_t cap = max_blocks ? max_blocks : kGroupMaxBlocks;
     CHECK(p.cap == cap && p.cap <= kGridX, AT);
     if (ngroups == 0 || gsg == 0 || kpg == 0) {               // nothing to do: no unit, no launch
         uint64_t n = 0;
-        p.for_each_launch([&](const GroupScatterLaunch&) { return ++n, 0; });
+        p.for_each_launch([&](const GroupLaunch&) { return ++n, 0; });
         CHECK(p.units() == 0 && p.passes() == 0 && n == 0, AT);
         return;
     }
@@ -61,8 +61,8 @@ static void check_plan(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg,
     CHECK(p.units() == ngroups * C * p.runs, AT);
     CHECK(p.route == scatter_route(ngroups, gsg, C, kpg), AT);        // the route is a function of the shape alone
     // Few large groups split into runs; groups enough to fill the chip do not (unless max_sg cuts them).
-    if (2 * ngroups * C <= cus * kGroupScatterPerCu && gsg >= 2) CHECK(p.runs > 1, AT);
-    if (ngroups * C >= cus * kGroupScatterPerCu && !max_sg) CHECK(p.runs == 1, AT);
+    if (2 * ngroups * C <= cus * kGroupPerCu && gsg >= 2) CHECK(p.runs > 1, AT);
+    if (ngroups * C >= cus * kGroupPerCu && !max_sg) CHECK(p.runs == 1, AT);
     const uint64_t triples = ngroups * gsg * C, lanes = ngroups * C;
     const bool exhaustive = triples <= (1u << 21);
     g_exhaustive += exhaustive;
@@ -70,15 +70,15 @@ static void check_plan(uint64_t ngroups, uint64_t gsg, uint32_t C, uint32_t kpg,
     std::vector<uint64_t> next(lanes);                      // per (group, column): where its next run must start
     uint32_t k_at = 0;                                      // keys [0, k_at) are done
     uint64_t u_at = p.units();                              // units [0, u_at) of the current pass are done
-    uint32_t pass_k0 = 0, pass_kp = 0, last_kp = kGroupScatterKeysPerPass, width_sum = 0;
+    uint32_t pass_k0 = 0, pass_kp = 0, last_kp = kGroupKeysPerPass, width_sum = 0;
     uint64_t passes = 0;
-    p.for_each_launch([&](const GroupScatterLaunch& l) {
+    p.for_each_launch([&](const GroupLaunch& l) {
         ++g_launches;
         if (u_at == p.units()) {                            // a new key pass
             for (uint64_t i = 0; i < lanes; ++i) CHECK(k_at == 0 || next[i] == gsg, AT);
-            CHECK(l.k0 == k_at && l.kp >= 1 && l.kp <= kGroupScatterKeysPerPass && l.k0 + l.kp <= kpg, AT);
-            CHECK(last_kp == kGroupScatterKeysPerPass, AT);   // 4s, then one last pass of the 1 to 3 keys left
-            CHECK(l.kp == kGroupScatterKeysPerPass || l.k0 + l.kp == kpg, AT);
+            CHECK(l.k0 == k_at && l.kp >= 1 && l.kp <= kGroupKeysPerPass && l.k0 + l.kp <= kpg, AT);
+            CHECK(last_kp == kGroupKeysPerPass, AT);   // 4s, then one last pass of the 1 to 3 keys left
+            CHECK(l.kp == kGroupKeysPerPass || l.k0 + l.kp == kpg, AT);
             pass_k0 = l.k0, pass_kp = l.kp, last_kp = l.kp, k_at = l.k0 + l.kp, u_at = 0;
             width_sum += l.kp;
             ++passes;
@@ -189,9 +189,9 @@ int main() {
     CHECK(plan_scatter_grouped(5, 3, 1, 1, 256, clamp_fold_limits(1023, 0)).cap == 1023, "cap");
     // 10^5 tiny groups are one grid per pass.
     {
-        const GroupedScatterPlan p = plan_scatter_grouped(100000, 1, 1, 1, 256, clamp_fold_limits(0, 0));
+        const GroupedPlan p = plan_scatter_grouped(100000, 1, 1, 1, 256, clamp_fold_limits(0, 0));
         uint64_t n = 0;
-        p.for_each_launch([&](const GroupScatterLaunch& l) { return ++n, (void)l, 0; });
+        p.for_each_launch([&](const GroupLaunch& l) { return ++n, (void)l, 0; });
         CHECK(n == 1 && p.units() == 100000, "one grid");
     }
     printf("plans=%llu launches=%llu exhaustive=%llu\n", (ull)g_plans, (ull)g_launches, (ull)g_exhaustive);

@@ -424,8 +424,9 @@ def _fold_grouped_plan(ng, kpg, nrec, rec):
 
 def _grouped_runs(ng, rec, nrec, cus):
     """Runs a group is cut into by the grouped fold's plan, restated from
-    plan_fold_grouped (csrc/pir_group_plan.hpp): whole pairs of super-groups,
-    about 8 workgroups per CU over the ng * columns cells of a key pass."""
+    plan_fold_grouped and grouped_want_runs (csrc/pir_group_plan.hpp, the
+    builder of the fold's GroupedPlan): whole pairs of super-groups, about 8
+    workgroups per CU over the ng * columns cells of a key pass."""
     gsg, cells = (nrec + 255) // 256, ng * ((rec + 31) // 32)
     want = max(1, min(gsg, -(-cus * 8 // cells)))
     per_run = (-(-gsg // want) + 1) // 2 * 2
