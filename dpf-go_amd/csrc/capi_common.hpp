@@ -3,7 +3,7 @@
 //                    the tree, Eval and Eval-bits entries, the form queries
 //   capi_pir.hip     every device-resident PIR form (slice and un-slice, fold, scatter,
 //                    answer, write, update / gather, the sparse composites,
-//                    the grouped forms)
+//                    the grouped forms, the grouped-sparse composites)
 //   capi_pir_db.hip  the resident-DB handle (create, answer, update / read, write,
 //                    the grouped write, export / merge / clear)
 // Here: the error slot, the device objects, and one definition of each
@@ -239,6 +239,30 @@ inline GroupWs group_ws(void* d_work, size_t nkeys, uint32_t stop) {
     return w;
 }
 
+// d_work of the two grouped-sparse composites: [Eval-bits workspace of all
+// nkeys = ngroups * kpg keys at nrec points each | bit rows
+// [nkeys][dpf_eval_bits_stride(nrec)] in group order | the grouped fold's
+// scratch], the first two parts rounded up to 16 bytes.  The rows keep the
+// Eval-bits stride: the grouped fold and scatter read no word past a row's end
+// (their wlim), so a 16-byte row (nrec <= 128) needs no rounding up to the
+// 32 bytes of a super-group's selection words.
+struct GroupSparseWs {
+    size_t eval_bytes, stride;
+    uint8_t* bits;
+    uint32_t* scratch;
+    size_t total;
+};
+inline GroupSparseWs group_sparse_ws(void* d_work, size_t nkeys, uint64_t nrec, uint32_t logN) {
+    GroupSparseWs w;
+    w.eval_bytes = align16(eval_ws_bytes(nkeys, nrec, logN));
+    w.stride = dpfh::eval_bits_stride(nrec);
+    const size_t rows = align16(nkeys * w.stride);
+    w.bits = at(d_work, w.eval_bytes);
+    w.scratch = (uint32_t*)at(d_work, w.eval_bytes + rows);
+    w.total = w.eval_bytes + rows + group_fold_ws_bytes();
+    return w;
+}
+
 // ---- expanded keys in a caller's d_work (dpf_capi.hip) -----------------------
 // Every entry point that expands keys into a caller's d_work records what it
 // left there (the tree_ws layout), so a later dpf_evalfull_expanded_dev never
@@ -258,10 +282,12 @@ inline hipError_t eval_unpack(const uint8_t* d_keys, size_t klen, size_t nkeys, 
     return dpfk::launch_unpack(d_keys, klen, nkeys, stop_of(logN), (uint32_t*)d_work, st);
 }
 
-// The launches of dpf_eval_bits_dev, arguments checked (dpf_capi.hip).
-hipError_t eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, const uint64_t* d_xs, size_t npts,
-                            uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
-                            hipStream_t st);
+// The launches of dpf_eval_bits_dev and dpf_eval_bits_grouped_dev, arguments
+// checked (dpf_capi.hip): key k at list k / keys_per_list of d_xs[][npts]
+// (keys_per_list = nkeys: one shared list).
+hipError_t eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, size_t keys_per_list, const uint64_t* d_xs,
+                            size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work,
+                            size_t work_bytes, hipStream_t st);
 
 // ---- argument rules ----------------------------------------------------------
 // The reference reads k[0:17], the level records k[17+18i : 17+18i+18] for
@@ -317,10 +343,24 @@ inline int check_sel_bits(size_t bits_stride, uint64_t nrec) {
     return DPF_OK;
 }
 
+// Bit rows an Eval-bits launch writes, bits_stride bytes a key: whole 16-byte
+// words that hold the span of npts points.
+inline int check_bits_rows(size_t bits_stride, size_t npts) {
+    if (bits_stride % 16 != 0 || bits_stride < dpfh::eval_bits_stride(npts))
+        return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16, at least dpf_eval_bits_stride(npts)");
+    return DPF_OK;
+}
+
 // A grouped call's key rows: ngroups * keys_per_group of them, counted in 32 bits.
 inline int check_group_keys(uint64_t ngroups, uint64_t keys_per_group) {
     if (ngroups != 0 && keys_per_group > (uint64_t)UINT32_MAX / ngroups)
         return fail(DPF_ERR_PARAM, "dpf: ngroups * keys_per_group does not fit 32 bits");
+    return DPF_OK;
+}
+
+// A grouped call's point lists [ngroups][npts]: their bytes fit 64 bits.
+inline int check_group_points(uint64_t ngroups, uint64_t npts) {
+    if (!dpfh::eval_bits_lists_ok(ngroups, npts)) return fail(DPF_ERR_PARAM, "dpf: ngroups * npts points do not fit 64 bits");
     return DPF_OK;
 }
 

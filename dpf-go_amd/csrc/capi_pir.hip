@@ -46,6 +46,14 @@ int check_answer_bufs(const void* d_keys, size_t nkeys, const void* d_db, uint64
     if (!aligned(16, d_db, d_work) || !aligned(4, d_ans)) return misaligned_buffer();
     return DPF_OK;
 }
+// The same with the records' points, which the call reads where it reads the
+// DB: every null buffer is reported before any misaligned one.
+int check_answer_bufs(const void* d_keys, size_t nkeys, const void* d_db, const void* d_points, uint64_t nrec,
+                      const void* d_ans, const void* d_work) {
+    if (nkeys > 0 && nrec > 0 && !present(d_points)) return null_buffer();
+    if (int rc = check_answer_bufs(d_keys, nkeys, d_db, nrec, d_ans, d_work)) return rc;
+    return aligned(8, d_points) ? DPF_OK : misaligned_buffer();
+}
 
 // The PIR answer of the five *_dev entries below: the subtree EvalFull into
 // the workspace (tree launch), then the fold over the DB of rec_bytes-wide
@@ -390,7 +398,7 @@ int dpf_pir_answer_sparse_dev(int device, const uint8_t* d_keys, size_t klen, si
         return DPF_OK;
     }
     const SparseWs w = sparse_ws(d_work, nkeys, nrec, logN);
-    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
     HIP_TRY(fold_launcher(true)((const uint32_t*)w.bits, w.stride / 4, d_dbs, nrec, rec_bytes, (uint32_t)nkeys,
                                 (uint32_t*)d_ans, w.parts, st));
     return DPF_OK;
@@ -408,7 +416,7 @@ int dpf_pir_write_sparse_dev(int device, const uint8_t* d_keys, size_t klen, siz
     CuScope cus(stream);
     hipStream_t st = (hipStream_t)stream;
     const SparseWs w = sparse_ws(d_work, nkeys, nrec, logN);
-    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, nkeys, d_points, nrec, logN, w.bits, w.stride, d_work, w.eval_bytes, st));
     HIP_TRY(scatter_launcher(true)((const uint32_t*)w.bits, w.stride / 4, d_dbs, nrec, rec_bytes, d_msgs, nkeys, st));
     return DPF_OK;
 }
@@ -569,6 +577,65 @@ int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint
     });
     form->launches = launches;
     form->pass_widths = widths;
+    return DPF_OK;
+}
+
+// ---- grouped keyword PIR: every group's records at its own points ----
+// The selection rows come from the Eval-bits launch with a list coordinate
+// (group g's keys at d_points[g][0 .. nrec)), not from a whole-domain tree
+// pass; the fold and the scatter are the grouped ones.
+size_t dpf_pir_grouped_sparse_workspace_size(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, uint32_t logN,
+                                             size_t rec_bytes) {
+    if (!rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK) return 0;
+    return group_sparse_ws(nullptr, ngroups * keys_per_group, nrec, logN).total;
+}
+
+int dpf_pir_answer_grouped_sparse_dev(int device, const uint8_t* d_keys, size_t klen, uint64_t ngroups,
+                                      uint64_t keys_per_group, uint32_t logN, const uint64_t* d_points,
+                                      const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                                      void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_key(klen, logN)) return rc;
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    if (int rc = check_group_points(ngroups, nrec)) return rc;
+    const size_t nkeys = ngroups * keys_per_group;
+    if (int rc = check_answer_bufs(d_keys, nkeys, d_dbs, d_points, nrec, d_ans, d_work)) return rc;
+    if (nkeys == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (nrec == 0) {
+        HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
+        return DPF_OK;
+    }
+    const GroupSparseWs w = group_sparse_ws(d_work, nkeys, nrec, logN);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, keys_per_group, d_points, nrec, logN, w.bits, w.stride, d_work,
+                             w.eval_bytes, st));
+    HIP_TRY(dpfk::launch_pir_fold_grouped((const uint32_t*)w.bits, w.stride / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
+                                          nrec, rec_bytes, (uint32_t*)d_ans, w.scratch, st));
+    return DPF_OK;
+}
+
+int dpf_pir_write_grouped_sparse_dev(int device, const uint8_t* d_keys, size_t klen, uint64_t ngroups,
+                                     uint64_t keys_per_group, uint32_t logN, const uint64_t* d_points,
+                                     const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, void* d_work,
+                                     void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_key(klen, logN)) return rc;
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    if (int rc = check_group_points(ngroups, nrec)) return rc;
+    if (!present(d_keys, d_points, d_msgs, d_dbs, d_work)) return null_buffer();
+    if (!aligned(16, d_msgs, d_dbs, d_work) || !aligned(8, d_points)) return misaligned_buffer();
+    const size_t nkeys = ngroups * keys_per_group;
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    const GroupSparseWs w = group_sparse_ws(d_work, nkeys, nrec, logN);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, keys_per_group, d_points, nrec, logN, w.bits, w.stride, d_work,
+                             w.eval_bytes, st));
+    HIP_TRY(dpfk::launch_scatter_grouped((const uint32_t*)w.bits, w.stride / 4, d_dbs, ngroups, (uint32_t)keys_per_group,
+                                         nrec, rec_bytes, d_msgs, st));
     return DPF_OK;
 }
 

@@ -36,6 +36,9 @@ struct PirDb {
     // groups of gnrec records, nrec = ngroups * gnrec the caller's index space.
     // Shard s holds the whole groups [group_lo(s), group_hi(s)), gps of them,
     // and `ranges` is in flat positions of the grouped layout (pir_group_plan.hpp).
+    // Grouped and sparse (dpf_pir_db_create_grouped_sparse): record i of group g
+    // lives at points[g][i]; a shard's groups' points [groups][gnrec], tight,
+    // sit beside it in HBM.
     bool grouped = false;
     uint64_t ngroups = 0, gnrec = 0, gps = 0;
     uint64_t group_lo(size_t s) const { return std::min<uint64_t>(ngroups, (uint64_t)s * gps); }
@@ -131,8 +134,9 @@ int upload_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t g, const uint
 // Shard s of a grouped handle under construction: its groups of db
 // [ngroups][gnrec][rec_bytes] go up through a staging buffer of whole groups
 // (at least one, however large) laid out as the flat DB, zero records behind
-// each group's gnrec, and are sliced into their place in the shard.
-int upload_grouped_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t s, const uint8_t* db) {
+// each group's gnrec, and are sliced into their place in the shard.  points
+// (the grouped keyword kind): the shard's groups' lists go up as they are.
+int upload_grouped_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t s, const uint8_t* db, const uint64_t* points) {
     const uint64_t g0 = h->group_lo(s), g1 = h->group_hi(s), n = h->gnrec, gs = dpfh::group_stride(n);
     const size_t w4 = h->w4, rb = h->rec_bytes;
     DeviceGuard gd(dev->id);
@@ -142,6 +146,14 @@ int upload_grouped_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t s, co
     h->devs.push_back(dev);
     h->shard.push_back(p);
     h->shard_n.push_back((g1 - g0) * gs);
+    if (h->sparse) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<uint64_t>((g1 - g0) * n, 2) * 8) != hipSuccess)
+            return fail(DPF_ERR_NOMEM, "dpf: DB shard allocation failed");
+        h->shard_pts.push_back(q);
+        if (g1 > g0 && n > 0 && hipMemcpy(q, points + g0 * n, (g1 - g0) * n * 8, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(DPF_ERR_HIP, "dpf: DB upload failed");
+    }
     if (g1 <= g0 || n == 0) return DPF_OK;
     const uint64_t per = std::max<uint64_t>(1, kPirUploadChunk / (gs * w4));   // groups per staging chunk
     uint8_t* tmp = nullptr;
@@ -164,17 +176,24 @@ int upload_grouped_shard(PirDb* h, const std::shared_ptr<Dev>& dev, size_t s, co
     return ok ? DPF_OK : fail(DPF_ERR_HIP, "dpf: DB upload failed");
 }
 
-// dpf_pir_db_create_grouped: what needs no device, the devices, the uploads.
-int pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t caller_bytes, uint32_t logN,
-                          int ngpus, void** handle) {
+// dpf_pir_db_create_grouped and, with sparse (every group's records at its own
+// points [ngroups][nrec]), dpf_pir_db_create_grouped_sparse: what needs no
+// device, the devices, the uploads.
+int pir_db_create_grouped(const uint64_t* points, bool sparse, const uint8_t* db, uint64_t ngroups, uint64_t nrec,
+                          size_t caller_bytes, uint32_t logN, int ngpus, void** handle) {
     if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
     *handle = nullptr;
     if (int rc = check_rec_bytes(RecRule::Bytes1, caller_bytes)) return rc;
-    if (logN > 63 || nrec > (1ull << logN)) return fail(DPF_ERR_PARAM, "dpf: group larger than 2^logN");
+    if (logN > 63 || (!sparse && nrec > (1ull << logN))) return fail(DPF_ERR_PARAM, "dpf: group larger than 2^logN");
     const size_t w4 = (caller_bytes + 3) & ~(size_t)3;
     uint64_t bytes = 0;
     if (!dpfh::grouped_bytes(ngroups, nrec, w4, &bytes)) return fail(DPF_ERR_PARAM, "dpf: grouped DB too large");
-    if (ngroups > 0 && nrec > 0 && !db) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    if (ngroups > 0 && nrec > 0 && (!db || (sparse && !points))) return fail(DPF_ERR_PARAM, "dpf: null buffer");
+    if (sparse) {
+        if (int rc = check_group_points(ngroups, nrec)) return rc;
+        for (uint64_t j = 0; j < ngroups * nrec; ++j)
+            if ((points[j] >> logN) != 0) return fail(DPF_ERR_PARAM, "dpf: point outside the 2^logN domain");
+    }
     int have = 0;
     const DevList devs = pick_devs(0, &have);
     if (have <= 0) return have;
@@ -187,12 +206,13 @@ int pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, si
     h->rec_bytes = caller_bytes;
     h->w4 = w4;
     h->grouped = true;
+    h->sparse = sparse;
     h->ngroups = ngroups;
     h->gnrec = nrec;
     h->gps = dpfh::groups_per_shard(ngroups, (size_t)want);
     h->ranges = dpfh::grouped_shards(ngroups, nrec, (size_t)want);
     for (int g = 0; g < want; ++g)
-        if (int rc = upload_grouped_shard(h.get(), devs[(size_t)g], (size_t)g, db)) return rc;
+        if (int rc = upload_grouped_shard(h.get(), devs[(size_t)g], (size_t)g, db, points)) return rc;
     *handle = h.release();
     return DPF_OK;
 }
@@ -255,9 +275,10 @@ int on_shard(PirDb* h, size_t s, const uint8_t* keys, size_t klen, size_t nkeys,
     DeviceGuard gd(d.id);
     HIP_TRY(d.keys.ensure(keys_bytes));
     // (The grouped workspace is a function of the key rows, groups x keys per group, alone.)
-    HIP_TRY(d.work.ensure(h->grouped  ? dpf_pir_grouped_workspace_size(1, nkeys, h->logN, h->w4)
-                          : h->sparse ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
-                                      : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
+    HIP_TRY(d.work.ensure(h->grouped && h->sparse ? dpf_pir_grouped_sparse_workspace_size(1, nkeys, h->gnrec, h->logN, h->w4)
+                          : h->grouped            ? dpf_pir_grouped_workspace_size(1, nkeys, h->logN, h->w4)
+                          : h->sparse             ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
+                                                  : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
     HIP_TRY(d.out.ensure(out_bytes));
     HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
     if (int rc = body(d)) return rc;
@@ -466,7 +487,11 @@ int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t
 }
 int dpf_pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes, uint32_t logN,
                               int ngpus, void** handle) {
-    return pir_db_create_grouped(db, ngroups, nrec, rec_bytes, logN, ngpus, handle);
+    return pir_db_create_grouped(nullptr, false, db, ngroups, nrec, rec_bytes, logN, ngpus, handle);
+}
+int dpf_pir_db_create_grouped_sparse(const uint64_t* points, const uint8_t* db, uint64_t ngroups, uint64_t nrec,
+                                     size_t rec_bytes, uint32_t logN, int ngpus, void** handle) {
+    return pir_db_create_grouped(points, true, db, ngroups, nrec, rec_bytes, logN, ngpus, handle);
 }
 
 size_t dpf_pir_db_rec_bytes(void* handle) { return handle ? ((PirDb*)handle)->rec_bytes : 0; }
@@ -490,9 +515,12 @@ int dpf_pir_answer(void* handle, const uint8_t* keys, size_t klen, size_t nkeys,
         if (nkeys == 0) return DPF_OK;
         if (!keys || !ans) return fail(DPF_ERR_PARAM, "dpf: null buffer");
         return on_group_shards(h, keys, klen, nkeys, false, [&](Dev& d, size_t s, uint64_t g0, uint64_t ng, size_t kpg) {
-            if (int r = dpf_pir_answer_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN,
-                                                   (const uint8_t*)h->shard[s], h->gnrec, w4, (uint8_t*)d.out.p, d.work.p,
-                                                   d.st))
+            const uint8_t *k = (const uint8_t*)d.keys.p, *db = (const uint8_t*)h->shard[s];
+            if (int r = h->sparse ? dpf_pir_answer_grouped_sparse_dev(d.id, k, klen, ng, kpg, h->logN,
+                                                                      (const uint64_t*)h->shard_pts[s], db, h->gnrec, w4,
+                                                                      (uint8_t*)d.out.p, d.work.p, d.st)
+                                  : dpf_pir_answer_grouped_dev(d.id, k, klen, ng, kpg, h->logN, db, h->gnrec, w4,
+                                                               (uint8_t*)d.out.p, d.work.p, d.st))
                 return r;
             HIP_TRY(copy_rows_down(ans + g0 * kpg * rb, d.out.p, w4, rb, ng * kpg, d.st));
             return (int)DPF_OK;
@@ -528,7 +556,7 @@ int dpf_pir_db_xor_records(void* handle, uint64_t first, uint64_t n, const uint8
     return pir_export_or_xor(handle, first, n, nullptr, recs);
 }
 
-// Every shard zeroed on its stream under its device's mutex; a sparse handle keeps its points.
+// Every shard zeroed on its stream under its device's mutex; a sparse or grouped keyword handle keeps its points.
 int dpf_pir_db_clear(void* handle) {
     PirDb* h = (PirDb*)handle;
     if (!h) return fail(DPF_ERR_PARAM, "dpf: null PIR handle");
@@ -583,8 +611,11 @@ int dpf_pir_db_write_grouped(void* handle, const uint8_t* keys, size_t klen, siz
     const size_t rb = h->rec_bytes, w4 = h->w4;
     return on_group_shards(h, keys, klen, nkeys, true, [&](Dev& d, size_t s, uint64_t g0, uint64_t ng, size_t kpg) {
         HIP_TRY(copy_rows_up(d.out.p, w4, msgs + g0 * kpg * rb, rb, ng * kpg, d.st));   // zero pad bytes: the DB's stay zero
-        return dpf_pir_write_grouped_dev(d.id, (const uint8_t*)d.keys.p, klen, ng, kpg, h->logN, (const uint8_t*)d.out.p,
-                                         (uint8_t*)h->shard[s], h->gnrec, w4, d.work.p, d.st);
+        const uint8_t *k = (const uint8_t*)d.keys.p, *m = (const uint8_t*)d.out.p;
+        uint8_t* db = (uint8_t*)h->shard[s];
+        return h->sparse ? dpf_pir_write_grouped_sparse_dev(d.id, k, klen, ng, kpg, h->logN, (const uint64_t*)h->shard_pts[s],
+                                                            m, db, h->gnrec, w4, d.work.p, d.st)
+                         : dpf_pir_write_grouped_dev(d.id, k, klen, ng, kpg, h->logN, m, db, h->gnrec, w4, d.work.p, d.st);
     });
 }
 

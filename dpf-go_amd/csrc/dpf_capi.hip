@@ -215,14 +215,14 @@ hipError_t dpfc::tree_from_keys(const uint8_t* d_keys, size_t klen, size_t nk, u
     return e;
 }
 
-hipError_t dpfc::eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, const uint64_t* d_xs, size_t npts,
-                                  uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
-                                  hipStream_t st) {
+hipError_t dpfc::eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, size_t keys_per_list,
+                                  const uint64_t* d_xs, size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride,
+                                  void* d_work, size_t work_bytes, hipStream_t st) {
     const EvalWs w = eval_ws(d_work, work_bytes, nkeys, logN);
     hipError_t e = eval_unpack(d_keys, klen, nkeys, logN, d_work, st);
     if (e != hipSuccess) return e;
-    return dpfk::launch_eval_bits((const uint32_t*)d_work, stop_of(logN), logN, d_xs, nkeys, npts, d_bits, bits_stride,
-                                  w.frontier, w.frontier_bytes, st);
+    return dpfk::launch_eval_bits((const uint32_t*)d_work, stop_of(logN), logN, d_xs, nkeys, keys_per_list, npts, d_bits,
+                                  bits_stride, w.frontier, w.frontier_bytes, st);
 }
 
 namespace {
@@ -636,16 +636,37 @@ int dpf_eval_bits_dev(int device, const uint8_t* d_keys, size_t klen, size_t nke
                       uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
                       void* stream) {
     if (int rc = check_key(klen, logN, false)) return rc;
-    if (bits_stride % 16 != 0 || bits_stride < dpfh::eval_bits_stride(npts))
-        return fail(DPF_ERR_PARAM, "dpf: bits_stride must be a multiple of 16, at least dpf_eval_bits_stride(npts)");
+    if (int rc = check_bits_rows(bits_stride, npts)) return rc;
     if (!aligned(8, d_xs) || !aligned(16, d_bits, d_work)) return misaligned_buffer();
     if (nkeys == 0 || npts == 0) return DPF_OK;
     if (!present(d_keys, d_xs, d_bits, d_work)) return null_buffer();
     if (int rc = check_eval_ws(eval_ws(d_work, work_bytes, nkeys, logN))) return rc;
     DeviceGuard g(device);
     CuScope cus(stream);
-    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, d_xs, npts, logN, d_bits, bits_stride, d_work, work_bytes,
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, nkeys, d_xs, npts, logN, d_bits, bits_stride, d_work, work_bytes,
                              (hipStream_t)stream));
+    return DPF_OK;
+}
+
+// The keys of group g at group g's own list of d_xs [ngroups][npts]: the same
+// kernel with a list coordinate (eval_bits_plan.hpp).  The checks come in the
+// grouped entries' order (capi_pir.hip).
+int dpf_eval_bits_grouped_dev(int device, const uint8_t* d_keys, size_t klen, uint64_t ngroups, uint64_t keys_per_group,
+                              const uint64_t* d_xs, size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride,
+                              void* d_work, size_t work_bytes, void* stream) {
+    if (int rc = check_bits_rows(bits_stride, npts)) return rc;
+    if (int rc = check_key(klen, logN)) return rc;
+    if (int rc = check_group_keys(ngroups, keys_per_group)) return rc;
+    if (int rc = check_group_points(ngroups, npts)) return rc;
+    const size_t nkeys = ngroups * keys_per_group;
+    if (nkeys > 0 && npts > 0 && !present(d_keys, d_xs, d_bits, d_work)) return null_buffer();
+    if (!aligned(8, d_xs) || !aligned(16, d_bits, d_work)) return misaligned_buffer();
+    if (nkeys == 0 || npts == 0) return DPF_OK;
+    if (int rc = check_eval_ws(eval_ws(d_work, work_bytes, nkeys, logN))) return rc;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(eval_bits_launch(d_keys, klen, nkeys, keys_per_group, d_xs, npts, logN, d_bits, bits_stride, d_work,
+                             work_bytes, (hipStream_t)stream));
     return DPF_OK;
 }
 

@@ -553,9 +553,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
     if (q0 < nq) eval_pair_walk<UNI>(ekeys, stop, logN, nq, pts_per_key, fseed, L, out, s_tab, q0, p);
 }
 
-// Eval of every key at one shared list of points, the answers as packed
-// selection bits: bit j % 8 of byte j / 8 of row `key` of bits[][bits_stride]
-// is Eval(key, xs[j]), EvalFull's bit order, so the rows feed the folds and
+// Eval of every key at a list of points, the answers as packed selection
+// bits: key k meets list k / keys_per_list of xs[][npts] (one shared list:
+// keys_per_list = nkeys; a grouped call: the keys of group g at group g's own
+// points), and bit j % 8 of byte j / 8 of row `key` of bits[][bits_stride]
+// is Eval(key, list[j]), EvalFull's bit order, so the rows feed the folds and
 // the scatter as EvalFull output does.  The mapping, the tail rule and what
 // the launch guarantees are written down in eval_bits_plan.hpp: wave w owns
 // unit w % units (128 points) of key w / units; lane l walks points 128 u + l
@@ -568,7 +570,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval2(const uint32_t* __restrict_
 // index, here and in pair_key, could truncate: their records alone are 256 GiB.)
 __global__ __launch_bounds__(kBlock, 4) void k_eval_bits(const uint32_t* __restrict__ ekeys, uint32_t stop,
                                                          uint32_t logN, const uint64_t* __restrict__ xs, uint64_t npts,
-                                                         uint64_t units, uint64_t nwaves,
+                                                         uint64_t keys_per_list, uint64_t units, uint64_t nwaves,
                                                          const uint4* __restrict__ fseed,
                                                          const uint8_t* __restrict__ ft, uint32_t L,
                                                          uint8_t* __restrict__ bits, uint64_t bits_stride) {
@@ -586,8 +588,13 @@ __global__ __launch_bounds__(kBlock, 4) void k_eval_bits(const uint32_t* __restr
         j0 = dpfh::eval_bits_point(unit, lane, 0);
         j1 = dpfh::eval_bits_point(unit, lane, 1);
         const uint32_t* ek = ekeys + key * ((uint64_t)(stop + 2) * 8);
-        p.x0 = xs[dpfh::eval_bits_clamp(j0, npts)];
-        p.x1 = xs[dpfh::eval_bits_clamp(j1, npts)];
+        // The key's own list: its index (below 2^32 as the key's is) and its
+        // base are wave-uniform and stay in scalar registers; the clamp is
+        // within the list, so a tail lane never reads the next list's points.
+        const uint32_t list = __builtin_amdgcn_readfirstlane((uint32_t)dpfh::eval_bits_list(key, keys_per_list));
+        const uint64_t* lx = xs + dpfh::eval_bits_list_base(list, npts);
+        p.x0 = lx[dpfh::eval_bits_clamp(j0, npts)];
+        p.x1 = lx[dpfh::eval_bits_clamp(j1, npts)];
         p.n0 = eval_start(ek, key, p.x0, logN, fseed, ft, L);
         p.n1 = eval_start(ek, key, p.x1, logN, fseed, ft, L);
     }
@@ -967,13 +974,13 @@ hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const u
 }
 
 hipError_t launch_eval_bits(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nkeys,
-                            uint64_t npts, uint8_t* bits, uint64_t bits_stride, void* frontier,
+                            uint64_t keys_per_list, uint64_t npts, uint8_t* bits, uint64_t bits_stride, void* frontier,
                             uint64_t frontier_bytes, hipStream_t st) {
     if (nkeys == 0 || npts == 0) return hipSuccess;
-    // The whole choice (frontier level, block, grid, units) is dpfh::eval_bits_form's.
+    // The whole choice (frontier level, block, grid, units, lists) is dpfh::eval_bits_form_lists'.
     dpfh::EvalBitsForm f;
-    if (!dpfh::eval_bits_form(nkeys, npts, stop, logN, frontier == nullptr ? 0 : frontier_bytes, (uint64_t)cu_count(),
-                              tree_knobs(), &f))
+    if (!dpfh::eval_bits_form_lists(nkeys, keys_per_list, npts, stop, logN, frontier == nullptr ? 0 : frontier_bytes,
+                                    (uint64_t)cu_count(), tree_knobs(), &f))
         return hipErrorInvalidValue;
     if (bits_stride % 16 != 0 || bits_stride < dpfh::eval_bits_stride(npts)) return hipErrorInvalidValue;
     const uint4* fseed = nullptr;
@@ -987,7 +994,7 @@ hipError_t launch_eval_bits(const uint32_t* ek, uint32_t stop, uint32_t logN, co
         ft = fts;
     }
     hipLaunchKernelGGL(k_eval_bits, dim3((uint32_t)f.grid), dim3(f.block), 0, st, ek, stop, logN, xs, (uint64_t)npts,
-                       f.units, f.nwaves, fseed, ft, f.L, bits, bits_stride);
+                       f.keys_per_list, f.units, f.nwaves, fseed, ft, f.L, bits, bits_stride);
     return hipGetLastError();
 }
 

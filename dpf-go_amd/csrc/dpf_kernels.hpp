@@ -83,12 +83,14 @@ uint64_t eval_frontier_bytes(uint64_t nkeys, uint32_t stop, uint64_t pts_per_key
 hipError_t launch_eval(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nq,
                        uint64_t pts_per_key, uint8_t* out, void* frontier, uint64_t frontier_bytes,
                        hipStream_t st);
-// Every key at the npts shared points xs, as selection-bit rows
-// bits[nkeys][bits_stride] (k_eval_bits; plan and layout: eval_bits_plan.hpp).
+// Key k at the npts points of list k / keys_per_list of xs[][npts] (nkeys a
+// multiple of keys_per_list; keys_per_list = nkeys: one shared list), as
+// selection-bit rows bits[nkeys][bits_stride] (k_eval_bits; plan and layout:
+// eval_bits_plan.hpp).
 // bits_stride: a multiple of 16, at least dpfh::eval_bits_stride(npts).  The
 // frontier is launch_eval's, sized eval_frontier_bytes(nkeys, stop, npts).
 hipError_t launch_eval_bits(const uint32_t* ek, uint32_t stop, uint32_t logN, const uint64_t* xs, uint64_t nkeys,
-                            uint64_t npts, uint8_t* bits, uint64_t bits_stride, void* frontier,
-                            uint64_t frontier_bytes, hipStream_t st);
+                            uint64_t keys_per_list, uint64_t npts, uint8_t* bits, uint64_t bits_stride,
+                            void* frontier, uint64_t frontier_bytes, hipStream_t st);
 
 }  // namespace dpfk

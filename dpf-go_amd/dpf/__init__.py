@@ -121,6 +121,11 @@ SIGNATURES = {
     "dpf_pir_write_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_write_grouped": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_scatter_grouped_form_for": (_int, [_u64, _u64, _u64, _sz, _int, ctypes.POINTER(ScatterGroupedFormC)]),
+    "dpf_eval_bits_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp]),
+    "dpf_pir_grouped_sparse_workspace_size": (_sz, [_u64, _u64, _u64, _u32, _sz]),
+    "dpf_pir_answer_grouped_sparse_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_write_grouped_sparse_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_create_grouped_sparse": (_int, [_u64p, _u8p, _u64, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_db_unslice_any_dev": (_int, [_int, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_unslice_grouped_dev": (_int, [_int, _vp, _u64, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_xor_sliced_dev": (_int, [_int, _vp, _vp, _sz, _vp]),
@@ -499,6 +504,17 @@ def eval_bits_dev(d_keys, key_len_: int, nkeys: int, d_xs, npts: int, logN: int,
     nbytes = int(d_work.numel() * d_work.element_size())
     _check(lib().dpf_eval_bits_dev(device, _ptr(d_keys), key_len_, nkeys, _ptr(d_xs), npts, logN, _ptr(d_bits),
                                    bits_stride, _ptr(d_work), nbytes, _stream_handle(stream)))
+
+
+def eval_bits_grouped_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: int, d_xs, npts: int, logN: int, d_bits,
+                          bits_stride: int, d_work, device: int = 0, stream=None) -> None:
+    """eval_bits_dev with a point list per group: d_xs is [ngroups][npts]
+    uint64, tight, and row g * keys_per_group + k of d_bits holds the bits of
+    that key at group g's own points (dpf_eval_bits_grouped_dev).  d_work is
+    sized as for eval_bits_dev with ngroups * keys_per_group keys."""
+    nbytes = int(d_work.numel() * d_work.element_size())
+    _check(lib().dpf_eval_bits_grouped_dev(device, _ptr(d_keys), key_len_, ngroups, keys_per_group, _ptr(d_xs), npts, logN,
+                                           _ptr(d_bits), bits_stride, _ptr(d_work), nbytes, _stream_handle(stream)))
 
 
 def expand_keys_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_work, device: int = 0, stream=None) -> None:
@@ -890,6 +906,31 @@ def scatter_grouped_form_for(ngroups: int, keys_per_group: int, nrec: int, rec_b
     return ScatterGroupedForm(*[int(getattr(c, f)) for f in ScatterGroupedForm._fields])
 
 
+# ---- grouped keyword PIR: every group's records at its own points ----
+def pir_grouped_sparse_workspace_size(ngroups: int, keys_per_group: int, nrec: int, logN: int, rec_bytes: int) -> int:
+    return int(lib().dpf_pir_grouped_sparse_workspace_size(ngroups, keys_per_group, nrec, logN, rec_bytes))
+
+
+def pir_answer_grouped_sparse_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: int, logN: int, d_points, d_dbs,
+                                  nrec: int, rec_bytes: int, d_ans, d_work, device: int = 0, stream=None) -> None:
+    """Record i of group g lives at d_points[g][i] (uint64 [ngroups][nrec],
+    tight): eval_bits_grouped_dev of all ngroups * keys_per_group keys (group
+    order) into d_work, then xor_fold_grouped_dev.  d_dbs is the grouped
+    layout; d_work holds pir_grouped_sparse_workspace_size bytes."""
+    _check(lib().dpf_pir_answer_grouped_sparse_dev(device, _ptr(d_keys), key_len_, ngroups, keys_per_group, logN,
+                                                   _ptr(d_points), _ptr(d_dbs), nrec, rec_bytes, _ptr(d_ans), _ptr(d_work),
+                                                   _stream_handle(stream)))
+
+
+def pir_write_grouped_sparse_dev(d_keys, key_len_: int, ngroups: int, keys_per_group: int, logN: int, d_points, d_msgs,
+                                 d_dbs, nrec: int, rec_bytes: int, d_work, device: int = 0, stream=None) -> None:
+    """The dual of pir_answer_grouped_sparse_dev: eval_bits_grouped_dev, then
+    xor_scatter_grouped_dev.  The same workspace."""
+    _check(lib().dpf_pir_write_grouped_sparse_dev(device, _ptr(d_keys), key_len_, ngroups, keys_per_group, logN,
+                                                  _ptr(d_points), _ptr(d_msgs), _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work),
+                                                  _stream_handle(stream)))
+
+
 # ---- whole-DB read-out: un-slice, XOR-merge ----
 def pir_db_unslice_any_dev(d_dbs, nrec: int, rec_bytes: int, d_db, device: int = 0, stream=None) -> None:
     """The inverse of pir_db_slice_any_dev: d_db [nrec][rec_bytes] row-major from
@@ -945,7 +986,17 @@ class PirDB:
     in group order (row g * kpg + j queries group g) and returns the answers
     in the same order; shards are ranges of whole groups over any number of
     GPUs; update()/read() take idx = g * nrec + i; write() is refused, the
-    private write of a grouped handle is write_grouped()."""
+    private write of a grouped handle is write_grouped().
+
+    With `points` and `groups=G` together the handle is the grouped keyword
+    kind (dpf_pir_db_create_grouped_sparse): `points` holds one uint64 per
+    record in group order, [G * nrec] or [G, nrec], and record i of group g
+    lives at domain point points[g][i] of a 2^logN domain (logN <= 63; nrec
+    may exceed 2^logN, points may repeat within a group).  The keys of group g
+    are evaluated at group g's own points in one launch for all groups.  In
+    every other respect it is a grouped handle: answer() and write_grouped()
+    take rows in group order, write() is refused, update() / read() / export()
+    / xor_records() take idx = g * nrec + i, and clear() keeps the points."""
 
     def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None, groups=None):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
@@ -956,12 +1007,17 @@ class PirDB:
         nrec = d.size // rec_bytes
         h = _vp()
         if groups is not None:
-            if points is not None:
-                raise ValueError("a PirDB is grouped or sparse, not both")
             if groups < 0 or (nrec % groups if groups else nrec):
                 raise ValueError("the DB must hold the same number of records for each of %d groups" % groups)
-            _check(lib().dpf_pir_db_create_grouped(_buf(d), groups, nrec // groups if groups else 0, rec_bytes, logN,
-                                                   ngpus, ctypes.byref(h)))
+            per = nrec // groups if groups else 0
+            if points is not None:
+                pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1)
+                if pts.size != nrec:
+                    raise ValueError("points must hold one uint64 per record")
+                _check(lib().dpf_pir_db_create_grouped_sparse(pts.ctypes.data_as(_u64p), _buf(d), groups, per, rec_bytes,
+                                                              logN, ngpus, ctypes.byref(h)))
+            else:
+                _check(lib().dpf_pir_db_create_grouped(_buf(d), groups, per, rec_bytes, logN, ngpus, ctypes.byref(h)))
         elif points is not None:
             pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1)
             if pts.size != nrec:
@@ -1064,7 +1120,7 @@ class PirDB:
         _check(lib().dpf_pir_db_xor_records(self._h, first, r.size // self.rec_bytes, _buf(r)))
 
     def clear(self) -> None:
-        """Every record := 0 (the next epoch's empty table); a sparse handle keeps its points."""
+        """Every record := 0 (the next epoch's empty table); a sparse or grouped keyword handle keeps its points."""
         _check(lib().dpf_pir_db_clear(self._h))
 
     def close(self) -> None:

@@ -15,6 +15,16 @@ records sends kpg short keys per bucket (write_plan: one per replica that falls
 into the bucket, dummies with an all-zero message in the unused slots) to
 `PirDB.write_grouped`, instead of m keys over the whole domain per replica.
 
+Keyword PIR over buckets (the keyword_* functions below): the records are keyed
+by keywords, not by an index.  A public hash sends a keyword to a point of a
+2^logN domain (logN 40 .. 63: large enough that two keywords do not collide)
+and further hashes send it to its nhash candidate buckets.  A bucket then holds
+its records at their keywords' points, the groups of
+`dpf.PirDB(bucket_db, logN, rec_bytes=rec, points=bucket_points, groups=nbuckets)`,
+and a client key for a bucket is Gen(point_of(keyword), logN): the servers
+evaluate every bucket's keys at that bucket's own points in one launch.  A
+keyword the table does not hold reads as the zero record.
+
 This is documentation that runs, not a protocol implementation: host-only,
 numpy-only, with a fixed integer mix in the place of a keyed hash, no
 treatment of failure probability and no padding of the number of queries.
@@ -53,12 +63,23 @@ def layout(n: int, nbuckets: int, nhash: int = 3, seed: int = 0) -> Layout:
     """Each record's candidate buckets, and its position inside each: the
     records of a bucket in index order (a record whose hashes collide on one
     bucket is stored there once per hash)."""
-    idx = np.arange(n, dtype=np.uint64)
+    return _layout_of(np.arange(n, dtype=np.uint64), nbuckets, nhash, seed)
+
+
+def _layout_of(idx: np.ndarray, nbuckets: int, nhash: int, seed: int, once: bool = False) -> Layout:
+    """layout() of records named by the uint64 values idx (their indices, or
+    their keywords).  once: a record whose hashes collide on one bucket is
+    stored there once, every colliding hash naming the same position."""
+    n = idx.size
     bucket = np.stack([(_mix(seed, j, idx) % np.uint64(nbuckets)).astype(np.int64) for j in range(nhash)], axis=1)
     pos = np.zeros((n, nhash), np.int64)
     fill = np.zeros(nbuckets, np.int64)
     for i in range(n):
         for j in range(nhash):
+            same = [k for k in range(j) if bucket[i, k] == bucket[i, j]] if once else []
+            if same:
+                pos[i, j] = pos[i, same[0]]
+                continue
             pos[i, j] = fill[bucket[i, j]]
             fill[bucket[i, j]] += 1
     return Layout(nbuckets, bucket, pos, int(fill.max()) if n else 0)
@@ -108,7 +129,7 @@ def alphas(assignment: dict, lay: Layout) -> np.ndarray:
     return a
 
 
-def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None):
+def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None, points=None, dummy=None):
     """(alphas [nbuckets][kpg] uint64, msgs [nbuckets][kpg][rec] uint8) for
     `PirDB.write_grouped`: {record: XOR delta (rec bytes)} turned into one key
     slot per replica of every record, at the replica's position in its bucket
@@ -117,12 +138,17 @@ def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None):
     which buckets are written.  rec_bytes is the record width; it may be left
     out where deltas is not empty (an empty one with rec_bytes is an all-dummy
     batch, cover traffic).  Raises BucketOverflow when a bucket holds more
-    replicas of the changed records than kpg."""
+    replicas of the changed records than kpg.  points ([n] uint64) and dummy
+    ([nbuckets] uint64) are keyword_write_plan's: a replica is then addressed
+    by its record's point instead of its position, a dummy slot of bucket b by
+    dummy[b] instead of 0."""
     items = [(int(r), np.ascontiguousarray(d, dtype=np.uint8).reshape(-1)) for r, d in deltas.items()]
     if rec_bytes is None and not items:
         raise ValueError("rec_bytes is needed where there are no deltas to take the width from")
     rec = int(rec_bytes) if rec_bytes is not None else items[0][1].size
     al = np.zeros((lay.nbuckets, kpg), np.uint64)
+    if dummy is not None:
+        al[:] = np.asarray(dummy, np.uint64).reshape(-1, 1)
     msgs = np.zeros((lay.nbuckets, kpg, rec), np.uint8)
     used = np.zeros(lay.nbuckets, np.int64)
     for r, d in items:
@@ -130,9 +156,93 @@ def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None):
             raise ValueError("every delta must be %d bytes wide" % rec)
         for j in range(lay.bucket.shape[1]):
             b = int(lay.bucket[r, j])
+            if points is not None and b in lay.bucket[r, :j]:
+                continue                                    # keyword_layout stores the record there once
             if used[b] == kpg:
                 raise BucketOverflow("bucket %d needs more than %d keys" % (b, kpg))
-            al[b, used[b]] = lay.pos[r, j]
+            al[b, used[b]] = lay.pos[r, j] if points is None else points[r]
             msgs[b, used[b]] = d
             used[b] += 1
     return al, msgs
+
+
+# ---- keyword PIR over buckets ------------------------------------------------
+_POINT_HASH = 63   # _mix's j of the keyword -> point hash (the bucket hashes use 0 .. nhash - 1)
+
+
+def keyword_points(keywords, logN: int, seed: int = 0) -> np.ndarray:
+    """[n] uint64: every keyword's point of the 2^logN domain (a public hash)."""
+    kw = np.ascontiguousarray(keywords, dtype=np.uint64).reshape(-1)
+    return _mix(seed, _POINT_HASH, kw) & np.uint64((1 << logN) - 1)
+
+
+def keyword_layout(keywords, nbuckets: int, nhash: int = 3, seed: int = 0) -> Layout:
+    """layout() by keyword: record i's candidate buckets are hashes of
+    keywords[i], so a client computes the candidates of a keyword it wants
+    (keyword_layout of its own short list) without knowing the table.  A
+    record whose hashes collide on one bucket is stored there ONCE (both
+    hashes name the same position): two replicas at one point of one bucket
+    would be selected together and cancel."""
+    return _layout_of(np.ascontiguousarray(keywords, dtype=np.uint64).reshape(-1), nbuckets, nhash, seed, once=True)
+
+
+def _absent_point(points: np.ndarray, logN: int) -> int:
+    """The smallest point of the 2^logN domain that is not in `points`."""
+    have = set(int(p) for p in points)
+    p = 0
+    while p in have:
+        p += 1
+    if p >> logN:
+        raise BucketOverflow("a bucket holds every point of the 2^%d domain" % logN)
+    return p
+
+
+def keyword_build(db: np.ndarray, keywords, lay: Layout, logN: int, seed: int = 0):
+    """(bucket_db [nbuckets][cap][rec], bucket_points [nbuckets][cap] uint64,
+    logN): the server's grouped keyword DB.  Slot lay.pos of a bucket holds a
+    replica of a record and its keyword's point.  A bucket shorter than cap is
+    padded: every pad slot is a zero record, and all pads of a bucket sit at
+    one repeated point that none of the bucket's records has.  Reads never see
+    a pad (it is zero, and no keyword of the bucket hashes to its point), but a
+    pad record absorbs a write aimed at its point: a key for that point with a
+    non-zero message would be XORed into every pad of the bucket, so writers
+    send dummies with an all-zero message only (keyword_write_plan does)."""
+    db = np.ascontiguousarray(db, dtype=np.uint8)
+    pts = keyword_points(keywords, logN, seed)
+    cap = max(lay.cap, 1)
+    out = np.zeros((lay.nbuckets, cap, db.shape[1]), np.uint8)
+    bpts = np.zeros((lay.nbuckets, cap), np.uint64)
+    fill = np.zeros(lay.nbuckets, np.int64)
+    for j in range(lay.bucket.shape[1]):
+        out[lay.bucket[:, j], lay.pos[:, j]] = db
+        bpts[lay.bucket[:, j], lay.pos[:, j]] = pts
+        np.maximum.at(fill, lay.bucket[:, j], lay.pos[:, j] + 1)
+    for b in range(lay.nbuckets):
+        if fill[b] < cap:
+            bpts[b, fill[b]:] = _absent_point(bpts[b, :fill[b]], logN)
+    return out, bpts, logN
+
+
+def keyword_alphas(assignment: dict, wanted_points, bucket_points: np.ndarray, logN: int) -> np.ndarray:
+    """[nbuckets] uint64: the point to query in every bucket.  assignment is
+    assign()'s {bucket: i} over the client's own list of wanted keywords
+    (keyword_layout of that list), wanted_points their points: bucket b is
+    asked for point_of(keyword i).  An unused bucket is asked for a point
+    absent from that bucket, which reads as zero.  The example looks one up in
+    bucket_points to be exact; a real client draws a random point of the
+    domain, which misses the bucket except with probability cap / 2^logN."""
+    a = np.array([_absent_point(bucket_points[b], logN) for b in range(bucket_points.shape[0])], np.uint64)
+    for b, i in assignment.items():
+        a[b] = wanted_points[i]
+    return a
+
+
+def keyword_write_plan(deltas: dict, lay: Layout, points, bucket_points: np.ndarray, logN: int, kpg: int,
+                       rec_bytes: int = None):
+    """write_plan() for the grouped keyword DB: {record: XOR delta} turned into
+    (alphas [nbuckets][kpg] uint64, msgs [nbuckets][kpg][rec]) for
+    `PirDB.write_grouped`, one slot per replica, addressed by the record's
+    point (points: keyword_points of the table's keywords).  Unused slots are
+    dummies at a point absent from their bucket with an all-zero message."""
+    dummy = np.array([_absent_point(bucket_points[b], logN) for b in range(bucket_points.shape[0])], np.uint64)
+    return write_plan(deltas, lay, kpg, rec_bytes, points=np.asarray(points, np.uint64), dummy=dummy)

@@ -181,6 +181,31 @@ size_t dpf_eval_bits_workspace_size(size_t nkeys, size_t npts, uint32_t logN);
 int dpf_eval_bits_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, const uint64_t* d_xs,
                       size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes,
                       void* stream);
+/* The same launch with a point list per group: d_keys is
+ * [ngroups * keys_per_group][key_len] in group order, d_xs is [ngroups][npts]
+ * uint64, tightly packed, and the keys of group g are evaluated at group g's
+ * own npts points: bit j of row g * keys_per_group + k of d_bits
+ * [ngroups * keys_per_group][bits_stride] is Eval(that key, d_xs[g][j], logN).
+ * The row contract is dpf_eval_bits_dev's: the first
+ * dpf_eval_bits_stride(npts) bytes of every row are written, bits at positions
+ * >= npts are zero, nothing past that span is touched; so the rows are valid
+ * d_bits input of dpf_xor_fold_grouped_dev and dpf_xor_scatter_grouped_dev
+ * with nrec = npts.  One kernel serves both entries (dpf_eval_bits_dev is the
+ * case of one list for all keys); a lane of a list's last, partial unit reads
+ * that list's last point and never the next list's.  The workspace is
+ * dpf_eval_bits_workspace_size(ngroups * keys_per_group, npts, logN), and with
+ * no more than the expanded keys every walk starts at the root; the bits are
+ * identical.  Checked before any device call, in the grouped entries' order:
+ * bits_stride (DPF_ERR_PARAM); logN > 63 (DPF_ERR_PARAM); the key length
+ * (DPF_ERR_KEYLEN); ngroups * keys_per_group not fitting 32 bits, or
+ * ngroups * npts * 8 bytes of points not fitting 64 (DPF_ERR_PARAM); a null
+ * buffer while there is work; a misaligned buffer (d_xs 8-byte, d_bits and
+ * d_work 16-byte); then ngroups, keys_per_group or npts == 0 returns DPF_OK
+ * without a launch, and a work_bytes that does not hold the expanded keys is
+ * DPF_ERR_PARAM.  Asynchronous on `stream`, capturable. */
+int dpf_eval_bits_grouped_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
+                              uint64_t keys_per_group, const uint64_t* d_xs, size_t npts, uint32_t logN,
+                              uint8_t* d_bits, size_t bits_stride, void* d_work, size_t work_bytes, void* stream);
 
 /* ---- Introspection: which form of a kernel a call runs -------------------
  * The tree kernel is one source but many kernels at run time; these say which
@@ -799,6 +824,66 @@ typedef struct dpf_scatter_grouped_form {
 } dpf_scatter_grouped_form;
 int dpf_scatter_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
                                  dpf_scatter_grouped_form* form);
+
+/* ---- Grouped keyword PIR: every group's records at its own points ---------
+ * The grouped and the sparse kinds composed: ngroups groups of nrec records,
+ * and record i of group g lives at domain point d_points[g][i], any point of a
+ * 2^logN domain with logN <= 63 (keywords hashed to points, cuckoo-hashed into
+ * buckets; or many keyword tables behind one server).  d_points is
+ * [ngroups][nrec] uint64, tightly packed: it is NOT padded to the group
+ * stride.  d_dbs is the grouped layout of dpf_pir_db_slice_grouped_dev (group
+ * stride dpf_pir_group_stride(nrec)); d_keys, d_ans and d_msgs are
+ * [ngroups * keys_per_group] rows in group order.  Points may repeat within a
+ * group (such records are selected together), and nrec > 2^logN is not an
+ * error, as for the sparse forms.
+ * Each composite is dpf_eval_bits_grouped_dev into a bit area inside d_work,
+ * then the grouped fold (dpf_xor_fold_grouped_dev) or the grouped scatter
+ * (dpf_xor_scatter_grouped_dev): launches by the batch, not by the group.  The
+ * bit rows keep the stride dpf_eval_bits_stride(nrec), also where that is 16
+ * bytes (nrec <= 128) and a super-group of 256 records would have 32: the
+ * grouped fold, like the scatter, reads no word past a row's end, so the rows
+ * are not rounded up and no gap is zeroed.
+ * d_work holds dpf_pir_grouped_sparse_workspace_size bytes: the Eval-bits
+ * workspace dpf_eval_bits_workspace_size(ngroups * keys_per_group, nrec, logN)
+ * rounded up to 16 bytes, ngroups * keys_per_group * dpf_eval_bits_stride(nrec)
+ * bytes of rows, and dpf_xor_fold_grouped_workspace_size(); 0 for a bad width
+ * or a key count that does not fit 32 bits.
+ * Checked before any device call, in this order: rec_bytes (DPF_ERR_PARAM);
+ * logN > 63 (DPF_ERR_PARAM); the key length (DPF_ERR_KEYLEN); ngroups *
+ * keys_per_group not fitting 32 bits, or the points' bytes not fitting 64
+ * (DPF_ERR_PARAM); null buffers (the answer allows those it has no work for,
+ * the write none, as the grouped write); misaligned buffers (d_dbs, d_msgs and
+ * d_work 16-byte, d_points 8-byte, d_ans 4-byte).  ngroups == 0 or
+ * keys_per_group == 0 returns DPF_OK without a launch; nrec == 0 makes the
+ * answer zero d_ans and the write a no-op.  Asynchronous on `stream` and
+ * capturable: no synchronisation, no allocation. */
+size_t dpf_pir_grouped_sparse_workspace_size(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, uint32_t logN,
+                                             size_t rec_bytes);
+int dpf_pir_answer_grouped_sparse_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
+                                      uint64_t keys_per_group, uint32_t logN, const uint64_t* d_points,
+                                      const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans,
+                                      void* d_work, void* stream);
+int dpf_pir_write_grouped_sparse_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
+                                     uint64_t keys_per_group, uint32_t logN, const uint64_t* d_points,
+                                     const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                                     void* d_work, void* stream);
+/* A resident DB of the grouped keyword kind: points [ngroups][nrec] and db
+ * [ngroups][nrec][rec_bytes], both tightly packed, every width 1 ..
+ * DPF_PIR_MAX_REC_BYTES (padded to a multiple of 4 on the device as
+ * dpf_pir_db_create_any does).  logN <= 63, and a point >= 2^logN is
+ * DPF_ERR_PARAM (*handle = NULL); nrec may exceed 2^logN and points may
+ * repeat.  Shards are ranges of whole groups exactly as
+ * dpf_pir_db_create_grouped cuts them, each with its groups' points beside it
+ * in HBM.  The handle is a grouped handle in every other respect:
+ * dpf_pir_answer and dpf_pir_db_write_grouped need nkeys to be a multiple of
+ * the groups, give each shard its groups' rows, do no host XOR, and run the
+ * two composites above; dpf_pir_db_write is DPF_ERR_PARAM; update, read,
+ * export, xor_records, clear, nrec, ngroups and rec_bytes keep the grouped
+ * handle's contracts with idx = g * nrec + i.  The points are fixed at
+ * creation and survive dpf_pir_db_clear.  With env DPF_PIR_FOLD=lds creation
+ * is DPF_ERR_PARAM. */
+int dpf_pir_db_create_grouped_sparse(const uint64_t* points, const uint8_t* db, uint64_t ngroups, uint64_t nrec,
+                                     size_t rec_bytes, uint32_t logN, int ngpus, void** handle);
 
 /* ---- Whole-DB read-out of a resident DB: un-slice, XOR-merge, clear -------
  * A DB that accumulates private writes (a mailbox, a bulletin board) is read
