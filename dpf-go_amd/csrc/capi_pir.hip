@@ -514,6 +514,40 @@ int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t klen, u
     return DPF_OK;
 }
 
+int dpf_fold_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
+                              dpf_fold_grouped_form* form) {
+    if (form == nullptr || !rec_bytes_ok(RecRule::Mul4, rec_bytes) || check_group_keys(ngroups, keys_per_group) != DPF_OK ||
+        nrec > UINT64_MAX - 255)
+        return fail(DPF_ERR_PARAM, "dpf: form query out of range");
+    const dpfh::GroupFoldKeysPlan p =
+        dpfk::fold_grouped_plan(ngroups, (uint32_t)keys_per_group, nrec, rec_bytes, (uint64_t)(cus > 0 ? cus : 0));
+    memset(form, 0, sizeof *form);
+    form->route = (uint32_t)p.route;
+    form->atomic = p.atomic();
+    form->max_blocks = p.cap;
+    uint64_t launches = 0;
+    if (p.route == dpfh::kFoldRouteMfma) {
+        const dpfh::GroupFoldPass t = p.tile(0);
+        form->columns_per_wg = t.cg;
+        form->keys_per_tile = 32u * (uint32_t)dpfh::kFoldTiles[t.shape].MT;
+        form->runs = t.runs;
+        form->sg_per_run = t.spr;
+        form->units = p.units(t);
+        form->passes = form->units ? p.tiles() : 0;
+        p.for_each_launch([&](const dpfh::GroupFoldLaunch&) { return ++launches, 0; });
+    } else {
+        form->columns_per_wg = 1;
+        form->keys_per_tile = p.direct.kp_max;
+        form->runs = p.direct.runs;
+        form->sg_per_run = p.direct.spr;
+        form->units = p.direct.units();
+        form->passes = p.direct.passes();
+        p.direct.for_each_launch([&](const dpfh::GroupLaunch&) { return ++launches, 0; });
+    }
+    form->launches = launches;
+    return DPF_OK;
+}
+
 // ---- grouped private writes: the dual of the grouped fold ----
 // The scatter has a group coordinate (launch_scatter_grouped), or loops the
 // dense scatter over the groups where its plan says so; no workspace.

@@ -1,5 +1,6 @@
 // fold_ops.hpp — pieces of the XOR fold shared by its translation units
-// (pir_fold_rows.hip, pir_fold_sliced.hip, pir_fold_grouped.hip, pir_scatter_grouped.hip, pir_db_ops.hip, pir_kernels.hip)
+// (pir_fold_rows.hip, pir_fold_sliced.hip, pir_fold_grouped.hip, pir_fold_grouped_mfma.hip, pir_scatter_grouped.hip,
+// pir_db_ops.hip, pir_kernels.hip)
 // and the fused PIR kernel (pir_fused.hip): the answers' clearing, the bitwise
 // and load helpers, the FP4 operands of the matrix-core fold (layout and
 // exactness: pir_fold_sliced.hip, "The fold as a GF(2) matrix product"), the

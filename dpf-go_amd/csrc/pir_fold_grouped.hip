@@ -1,13 +1,15 @@
 // pir_fold_grouped.hip — the grouped XOR fold: one launch answers many small
 // DBs (groups), each with its own keys.  The layout rule and the launch plan
-// are in pir_group_plan.hpp; the launcher walks the plan.
+// are in pir_group_plan.hpp; the launcher walks the plan.  Many keys per group
+// go to the matrix-core grouped fold (pir_fold_grouped_mfma.hip) by the route
+// rule of pir_group_fold_plan.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "dpf_kernels.hpp"
 #include "fold_ops.hpp"
-#include "pir_group_plan.hpp"
+#include "pir_group_fold_plan.hpp"
 #include "pir_kernels.hpp"
 
 namespace dpfk {
@@ -98,7 +100,22 @@ uint32_t group_kp_knob() {
     return kp;
 }
 
+// DPF_GROUP_FOLD_ROUTE = direct | mfma: the route whatever the plan's rule says,
+// for every caller of the public entries and in what the form query reports
+// (measurement only, named in include/dpf_hip.h; read at every call, so one
+// process can time both).
+int route_knob() {
+    const char* e = getenv("DPF_GROUP_FOLD_ROUTE");
+    return !e ? -1 : e[0] == 'd' ? (int)dpfh::kFoldRouteDirect : e[0] == 'm' ? (int)dpfh::kFoldRouteMfma : -1;
+}
+
 }  // namespace
+
+dpfh::GroupFoldKeysPlan fold_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes,
+                                          uint64_t cus) {
+    return dpfh::plan_fold_grouped_keys(ngroups, dpfh::group_stride(nrec) / 256, dpfh::rec_cols(rec_bytes), keys_per_group,
+                                        cus ? cus : (uint64_t)cu_count(), fold_limits(), route_knob(), group_kp_knob());
+}
 
 hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t ngroups,
                                    uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, uint32_t* ans,
@@ -110,10 +127,11 @@ hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key,
     const uint64_t ans_bytes = ngroups * keys_per_group * rec_bytes;
     if (nrec == 0) return launch_zero(ans, ans_bytes, st);
     if (words_per_key % 4 != 0 || words_per_key * 32 < nrec) return hipErrorInvalidValue;
-    const uint64_t gsg = dpfh::group_stride(nrec) / 256;
-    const uint32_t C = dpfh::rec_cols(rec_bytes), T = dpfh::rec_tiles(rec_bytes);
-    const dpfh::GroupedPlan p =
-        dpfh::plan_fold_grouped(ngroups, gsg, C, keys_per_group, (uint64_t)cu_count(), fold_limits(), group_kp_knob());
+    const uint32_t T = dpfh::rec_tiles(rec_bytes);
+    const dpfh::GroupFoldKeysPlan keys = fold_grouped_plan(ngroups, keys_per_group, nrec, rec_bytes, 0);
+    if (keys.route == dpfh::kFoldRouteMfma)
+        return launch_fold_grouped_mfma(keys, bits, words_per_key, dbs, rec_bytes, ans, st);
+    const dpfh::GroupedPlan& p = keys.direct;
     if (p.atomic())
         if (hipError_t e = launch_zero(ans, ans_bytes, st); e != hipSuccess) return e;
     return p.for_each_launch([&](const dpfh::GroupLaunch& l) {

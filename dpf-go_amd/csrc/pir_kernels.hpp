@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "pir_fold_plan.hpp"
+#include "pir_group_fold_plan.hpp"
 #include "pir_group_scatter_plan.hpp"
 
 namespace dpfk {
@@ -65,13 +66,24 @@ hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, 
 // g * keys_per_group + j selecting within group g (bit i = record i of the
 // group), and ans [ngroups * keys_per_group][rec_bytes] in the same order,
 // overwritten; zeros when nrec == 0.  The keys of a group share each read of
-// its tiles, up to 4 per pass.  words_per_key a multiple of 4 covering nrec
-// bits; ngroups * keys_per_group fits 32 bits.  `parts` is not written: runs
-// of one group combine by atomic XOR into answers cleared earlier in stream
-// order.  bits, dbs 16-byte, ans 4-byte aligned.
+// its tiles, up to 4 per pass; from dpfh::kGroupFoldMfmaMinKeys keys per group
+// (the route rule of pir_group_fold_plan.hpp) up to 256 per pass on the matrix
+// cores (k_fold_grouped_mfma, pir_fold_grouped_mfma.hip).  words_per_key a
+// multiple of 4 covering nrec bits; ngroups * keys_per_group fits 32 bits.
+// `parts` is not written on either route: runs of one group combine by atomic
+// XOR into answers cleared earlier in stream order.  bits, dbs 16-byte, ans
+// 4-byte aligned.
 hipError_t launch_pir_fold_grouped(const uint32_t* bits, uint64_t words_per_key, const uint8_t* dbs, uint64_t ngroups,
                                    uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes, uint32_t* ans,
                                    uint32_t* parts, hipStream_t st);
+// The plan that call walks: under the current limits, on `cus` CUs (0: the
+// calling thread's budget), its route after the DPF_GROUP_FOLD_ROUTE knob.
+dpfh::GroupFoldKeysPlan fold_grouped_plan(uint64_t ngroups, uint32_t keys_per_group, uint64_t nrec, uint64_t rec_bytes,
+                                          uint64_t cus);
+// The launches of p's matrix-core route (p.gsg > 0, p.kpg > 0): the clear where
+// p.atomic(), then every key tile's.  Same buffers as launch_pir_fold_grouped.
+hipError_t launch_fold_grouped_mfma(const dpfh::GroupFoldKeysPlan& p, const uint32_t* bits, uint64_t words_per_key,
+                                    const uint8_t* dbs, uint64_t rec_bytes, uint32_t* ans, hipStream_t st);
 
 // Records of a resident DB changed and read back in place (k_update_sliced,
 // k_gather_sliced).  Update: record idx[i] := recs[i * rec_bytes ..) for

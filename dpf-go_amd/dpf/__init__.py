@@ -74,6 +74,12 @@ class ScatterGroupedFormC(ctypes.Structure):
                 ("sg_per_run", _u64), ("units", _u64), ("max_blocks", _u64), ("passes", _u64), ("launches", _u64)]
 
 
+class FoldGroupedFormC(ctypes.Structure):
+    """dpf_fold_grouped_form (include/dpf_hip.h)."""
+    _fields_ = [("route", _u32), ("columns_per_wg", _u32), ("keys_per_tile", _u32), ("atomic", _u32), ("runs", _u64),
+                ("sg_per_run", _u64), ("units", _u64), ("passes", _u64), ("launches", _u64), ("max_blocks", _u64)]
+
+
 # name -> (restype, argtypes); must cover every function in include/dpf_hip.h
 SIGNATURES = {
     "dpf_tree_form_for": (_int, [_sz, _u32, _u32, _u32, _int, ctypes.POINTER(TreeFormC)]),
@@ -121,6 +127,7 @@ SIGNATURES = {
     "dpf_pir_write_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_write_grouped": (_int, [_vp, _u8p, _sz, _sz, _u8p]),
     "dpf_scatter_grouped_form_for": (_int, [_u64, _u64, _u64, _sz, _int, ctypes.POINTER(ScatterGroupedFormC)]),
+    "dpf_fold_grouped_form_for": (_int, [_u64, _u64, _u64, _sz, _int, ctypes.POINTER(FoldGroupedFormC)]),
     "dpf_eval_bits_grouped_dev": (_int, [_int, _vp, _sz, _u64, _u64, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp]),
     "dpf_pir_grouped_sparse_workspace_size": (_sz, [_u64, _u64, _u64, _u32, _sz]),
     "dpf_pir_answer_grouped_sparse_dev": (_int, [_int, _vp, _sz, _u64, _u64, _u32, _vp, _vp, _u64, _sz, _vp, _vp, _vp]),
@@ -904,6 +911,21 @@ def scatter_grouped_form_for(ngroups: int, keys_per_group: int, nrec: int, rec_b
     c = ScatterGroupedFormC()
     _check(lib().dpf_scatter_grouped_form_for(ngroups, keys_per_group, nrec, rec_bytes, cus, ctypes.byref(c)))
     return ScatterGroupedForm(*[int(getattr(c, f)) for f in ScatterGroupedForm._fields])
+
+
+FOLD_GROUPED_DIRECT, FOLD_GROUPED_MFMA = 0, 1
+FoldGroupedForm = collections.namedtuple(
+    "FoldGroupedForm", "route columns_per_wg keys_per_tile atomic runs sg_per_run units passes launches max_blocks")
+
+
+def fold_grouped_form_for(ngroups: int, keys_per_group: int, nrec: int, rec_bytes: int, cus: int = 0) -> "FoldGroupedForm":
+    """What xor_fold_grouped_dev launches for this shape under the current fold
+    limits and env DPF_GROUP_FOLD_ROUTE (dpf_fold_grouped_form_for): the direct
+    route of up to 4 keys per pass or the matrix-core route of up to 256.
+    Needs no device when cus > 0."""
+    c = FoldGroupedFormC()
+    _check(lib().dpf_fold_grouped_form_for(ngroups, keys_per_group, nrec, rec_bytes, cus, ctypes.byref(c)))
+    return FoldGroupedForm(*[int(getattr(c, f)) for f in FoldGroupedForm._fields])
 
 
 # ---- grouped keyword PIR: every group's records at its own points ----

@@ -129,6 +129,27 @@ def alphas(assignment: dict, lay: Layout) -> np.ndarray:
     return a
 
 
+def merge_clients(keys_per_client) -> np.ndarray:
+    """[nbuckets * nclients][key_len] in group order from a list of per-client
+    [nbuckets][key_len] key arrays: a server that batches the queries of several
+    clients answers them as keys_per_group = nclients keys per bucket, row
+    b * nclients + c being client c's key for bucket b.  Many keys per group are
+    one matrix-core pass over the buckets per 256 clients."""
+    ks = [np.ascontiguousarray(k, dtype=np.uint8) for k in keys_per_client]
+    if not ks or any(k.ndim != 2 or k.shape != ks[0].shape for k in ks):
+        raise ValueError("every client sends one [nbuckets][key_len] array of the same shape")
+    return np.ascontiguousarray(np.stack(ks, axis=1)).reshape(ks[0].shape[0] * len(ks), ks[0].shape[1])
+
+
+def split_answers(ans, nclients: int) -> np.ndarray:
+    """[nclients][nbuckets][rec]: merge_clients' inverse on the answers
+    [nbuckets * nclients][rec] of the merged keys; entry c is client c's."""
+    ans = np.ascontiguousarray(ans)
+    if nclients <= 0 or ans.ndim != 2 or ans.shape[0] % nclients:
+        raise ValueError("answers are [nbuckets * nclients][rec]")
+    return np.ascontiguousarray(ans.reshape(ans.shape[0] // nclients, nclients, ans.shape[1]).transpose(1, 0, 2))
+
+
 def write_plan(deltas: dict, lay: Layout, kpg: int, rec_bytes: int = None, points=None, dummy=None):
     """(alphas [nbuckets][kpg] uint64, msgs [nbuckets][kpg][rec] uint8) for
     `PirDB.write_grouped`: {record: XOR delta (rec bytes)} turned into one key

@@ -706,6 +706,17 @@ int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t
  * nrec records.  d_work holds dpf_xor_fold_grouped_workspace_size(ngroups,
  * keys_per_group, rec_bytes) bytes.  dpf_set_fold_limits' max_blocks, where
  * below its default, caps the workgroups of each of its launches.
+ * Keys per group: up to 4 keys of a group share one pass over its tiles (one
+ * launch per pass for all groups).  Many keys per group (from 5: the route
+ * rule of csrc/pir_group_fold_plan.hpp), the clients of a batched server for
+ * instance, take the matrix-core grouped fold instead: one pass and one
+ * launch per 256 keys of every group, with dpf_set_fold_limits'
+ * max_sg_per_block bounding a workgroup's run as in the dense matrix-core
+ * fold; the workspace is the same and is not written.  Env
+ * DPF_GROUP_FOLD_ROUTE=direct|mfma, read at every call, forces the route for
+ * every caller of the grouped fold, the grouped answers and the grouped
+ * handles (measurement only; leave it unset).  dpf_fold_grouped_form_for below
+ * tells which route a shape takes.
  * dpf_pir_answer_grouped_dev: d_keys is [ngroups * keys_per_group][key_len] in
  * that order; one tree pass of all the keys over the whole 2^logN domain into
  * a bit area inside d_work, then the grouped fold.  DPF_PIR_FUSED has no part
@@ -733,6 +744,31 @@ size_t dpf_pir_grouped_workspace_size(uint64_t ngroups, uint64_t keys_per_group,
 int dpf_pir_answer_grouped_dev(int device, const uint8_t* d_keys, size_t key_len, uint64_t ngroups,
                                uint64_t keys_per_group, uint32_t logN, const uint8_t* d_dbs, uint64_t nrec,
                                size_t rec_bytes, uint8_t* d_ans, void* d_work, void* stream);
+/* What dpf_xor_fold_grouped_dev launches for a shape under the current
+ * dpf_set_fold_limits, on `cus` CUs (<= 0: the current device's / the calling
+ * thread's stream budget; needs no device when cus > 0) and, like the call
+ * itself, under env DPF_GROUP_FOLD_ROUTE where set.  DPF_ERR_PARAM for a bad
+ * width, a key count that does not fit 32 bits or a null form; ngroups == 0,
+ * keys_per_group == 0 or nrec == 0 has launches == 0 (the clear of nrec == 0
+ * is not counted).  Where the keys of a group take several key tiles of
+ * different shapes, columns_per_wg, keys_per_tile, runs, sg_per_run and units
+ * are those of the first (the widest) tile. */
+#define DPF_FOLD_GROUPED_DIRECT 0 /* up to 4 keys of a group per pass over the DB */
+#define DPF_FOLD_GROUPED_MFMA 1   /* the matrix-core grouped fold: up to 256 keys per pass */
+typedef struct dpf_fold_grouped_form {
+    uint32_t route;          /* DPF_FOLD_GROUPED_* above */
+    uint32_t columns_per_wg; /* 32-byte columns a workgroup folds (1 on the direct route) */
+    uint32_t keys_per_tile;  /* keys of a group per pass at the most: 4 (direct), 32 .. 256 (the tile shape) */
+    uint32_t atomic;         /* 1: the answers are cleared first and the runs' words XORed in atomically */
+    uint64_t runs;           /* workgroups per (group, column group) */
+    uint64_t sg_per_run;     /* super-groups per run (the last run: what is left) */
+    uint64_t units;          /* workgroups per pass */
+    uint64_t passes;         /* passes over the DB: key passes (direct) or key tiles */
+    uint64_t launches;       /* fold launches of all passes (the clear is not counted) */
+    uint64_t max_blocks;     /* workgroups per launch at the most */
+} dpf_fold_grouped_form;
+int dpf_fold_grouped_form_for(uint64_t ngroups, uint64_t keys_per_group, uint64_t nrec, size_t rec_bytes, int cus,
+                              dpf_fold_grouped_form* form);
 /* A resident DB of the grouped kind: db [ngroups][nrec][rec_bytes], tightly
  * packed, every width 1 .. DPF_PIR_MAX_REC_BYTES (padded to a multiple of 4
  * on the device as dpf_pir_db_create_any does); logN <= 63 and nrec <= 2^logN
