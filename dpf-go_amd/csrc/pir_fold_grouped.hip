@@ -14,16 +14,16 @@
 
 namespace dpfk {
 
-// The popcount fold of k_fold_sliced_direct with a group coordinate.  Workgroup
+// The popcount fold (fold_popcount_body.inc: the loop this kernel shares
+// with k_fold_sliced_direct) with a group coordinate.  Workgroup
 // x of the launch is unit u0 + x of the plan (dpfh::group_unit): run
 // u % runs of column (u / runs) % C of group u / (runs * C), the group-local
 // super-groups [s0, s1) of that run.  Thread n of its 256 owns bit row n of the
 // column; per super-group it reads its 8 words once (the workgroup: 8 KiB
-// contiguous, flat super-group g * gsg + S) and, for each of the KP keys
-// k0 .. k0 + KP - 1 of the group, XORs (word & selection word) into that key's
-// accumulator: one v_bitop3 per word and key.  The selection words are
-// wave-uniform (scalar loads) from row g * kpg + k0 + j of bits; word 8 S + w
-// of a row is super-group S of the GROUP.  A row has wlim words: fewer than a
+// contiguous, flat super-group g * gsg + S) and folds them for each of the KP
+// keys k0 .. k0 + KP - 1 of the group.  Key j's selection words are row
+// g * kpg + k0 + j of bits; word 8 S + w of a row is super-group S of the
+// GROUP.  A row has wlim words: fewer than a
 // super-group's 8 at logN 7, and an end inside the last super-group whenever
 // the row is not a multiple of 256 bits; words past it select nothing.
 // Any width: thread n of column c has a row only if 256 c + n < nrows
@@ -46,47 +46,18 @@ __global__ __launch_bounds__(256) void k_fold_grouped(const uint32_t* __restrict
     const uint32_t col = un.c;
     const uint64_t key0 = g * kpg + k0;                         // first answer / selection row of this pass
     const uint32_t* sel = bits + key0 * wlim;
-    uint32_t acc[KP];
-#pragma unroll
-    for (int j = 0; j < KP; ++j) acc[j] = 0;
-    auto fold = [&](uint64_t S, const uint4& a, const uint4& b) __attribute__((always_inline)) {
-        const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        if (8 * S + 8 <= wlim) {                               // uniform
-#pragma unroll
-            for (int j = 0; j < KP; ++j)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) acc[j] = xam(acc[j], x[q], sel[j * wlim + 8 * S + q]);
-        } else {                                               // the key rows end inside this super-group
-#pragma unroll
-            for (int j = 0; j < KP; ++j)
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    if (8 * S + q < wlim) acc[j] = xam(acc[j], x[q], sel[j * wlim + 8 * S + q]);
-        }
-    };
-    const uint64_t row = (uint64_t)col * 256 + n;
-    auto at = [&](uint64_t S) { return group_tile(dbs, g, gsg, S, nrows, row); };
-    if (row < nrows) {
-        uint64_t S = s0;
-        for (; S + 1 < s1; S += 2) {
-            const uint4 a0 = at(S)[0], b0 = at(S)[1];
-            const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
-            fold(S, a0, b0);
-            fold(S + 1, a1, b1);
-        }
-        if (S < s1) fold(S, at(S)[0], at(S)[1]);
+#define FOLD_SEL(j, i) sel[j * wlim + i]
+#define FOLD_AT(S) group_tile(dbs, g, gsg, S, nrows, row)
+    // lanes 0 and 1 of a wave: its two answer words
+#define FOLD_EMIT_BEGIN const uint32_t word = 8 * col + 2 * w + l;
+#define FOLD_EMIT(j, m)                                            \
+    if (l < 2 && word < ntiles) {                                  \
+        const uint32_t v = l ? (uint32_t)(m >> 32) : (uint32_t)m; \
+        uint32_t* out = ans + (key0 + j) * ntiles + word;          \
+        if (!atomic) *out = v;                                     \
+        else if (v) atomicXor(out, v);                             \
     }
-    const uint32_t word = 8 * col + 2 * w + l;                  // lanes 0 and 1 of a wave: its two answer words
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc[j]) & 1) != 0);
-        if (l < 2 && word < ntiles) {
-            const uint32_t v = l ? (uint32_t)(m >> 32) : (uint32_t)m;
-            uint32_t* out = ans + (key0 + j) * ntiles + word;
-            if (!atomic) *out = v;
-            else if (v) atomicXor(out, v);
-        }
-    }
+#include "fold_popcount_body.inc"
 }
 
 namespace {

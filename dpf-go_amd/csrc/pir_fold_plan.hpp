@@ -201,6 +201,26 @@ inline int fold_tile_index(uint32_t nk, int cg) {
     if (nk <= 128) return cg >= 2 ? 4 : 5;
     return 6;
 }
+// The one dispatch from a run-time tile index to code compiled per shape:
+// calls f(FoldTileIndex<I>{}) for I = shape (an index past the table takes the
+// last shape) and returns what it returns.
+template <int I>
+struct FoldTileIndex {
+    static constexpr int value = I;
+};
+template <class F>
+auto with_fold_tile(int shape, F&& f) {
+    static_assert(kFoldTileCount == 7, "one case per tile shape");
+    switch (shape) {
+        case 0: return f(FoldTileIndex<0>{});
+        case 1: return f(FoldTileIndex<1>{});
+        case 2: return f(FoldTileIndex<2>{});
+        case 3: return f(FoldTileIndex<3>{});
+        case 4: return f(FoldTileIndex<4>{});
+        case 5: return f(FoldTileIndex<5>{});
+        default: return f(FoldTileIndex<6>{});
+    }
+}
 
 // The DB pieces of a matrix-core fold over at least nt_min DB bytes are
 // loaded nontemporal.  r05 (tools/archive/r05_nt.sh, profiles/r05/fold_nt/, B = 64,

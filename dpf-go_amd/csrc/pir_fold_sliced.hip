@@ -99,135 +99,36 @@ namespace dpfk {
 // FULL: the record is whole columns (T = 8 C, a multiple of 32 bytes), every
 // tile exists and the guards fold away: the kernel from before records of any
 // width (with the guards in, 64-byte records measured 2 % slower at 64 keys).
+//
+// The loop itself -- wave decode, staging, block loop, operands, MFMA nest,
+// ballots -- is fold_mfma_body.inc, shared as text with k_fold_grouped_mfma.
+// What is the dense kernel's own is below, as the macros that file names: the
+// answers' clearing, the column group and the run from the grid, the any-width
+// tile address, and partials.
 template <int MT, int NT, int SG, int CG, bool NTDB, int WPE, bool FULL>
 __global__ __launch_bounds__(64 * (8 / NT) * CG, WPE) void k_fold_mfma(
     const uint32_t* __restrict__ bits, uint64_t wpk, const uint4* __restrict__ dbs, uint64_t nsg, uint32_t nkeys,
     uint64_t sg_per_block, uint32_t* __restrict__ parts, uint32_t* __restrict__ zero, uint64_t zero_words,
     uint64_t wlim, uint32_t ntiles, uint32_t cg0) {
-    constexpr int NS = 8 / NT;                                 // bit slices of a column
-    constexpr int NW = NS * CG;
-    constexpr bool SC = NT < MT;                               // the selection side takes the cheap expansion
-    constexpr int kRows = 32 * MT;
-    constexpr int kRow = SG * 8 + 4;                           // words per staged row (+4: conflict-free b128 reads)
-    constexpr int kPieces = kRows * (SG * 2);                  // uint4 pieces per staged block
-    constexpr int kPer = (kPieces + 64 * NW - 1) / (64 * NW);  // per thread
-    __shared__ __attribute__((aligned(16))) uint32_t s_sel[kRows * kRow];
     zero_answers(blockIdx.y == 0 ? zero : nullptr, zero_words);
-    const uint32_t l = threadIdx.x & 63, h = l >> 5, r = l & 31;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t w = wv % NS, cw = wv / NS;                   // bit slice, column of the group
-    const uint64_t col = (uint64_t)(cg0 + blockIdx.y) * CG + cw;
-    const uint64_t tile0 = 8 * col + w * NT;                    // this wave's first bit tile
-    const uint32_t nt =                                         // how many of its NT tiles the record has
-        FULL ? (uint32_t)NT
-             : __builtin_amdgcn_readfirstlane(tile0 >= ntiles               ? 0u
-                                              : ntiles - tile0 < (uint64_t)NT ? (uint32_t)(ntiles - tile0)
-                                                                              : (uint32_t)NT);
-    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
-    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
-    if (s0 >= s1) return;                                       // uniform over the workgroup
-    auto load_sel = [&](uint64_t sb, uint4 (&v)[kPer]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < kPer; ++i) {
-            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
-            const uint32_t row = p / (2 * SG), q = p % (2 * SG);
-            const uint64_t word = sb * 8 + 4 * q;
-            const bool ok = p < (uint32_t)kPieces && row < nkeys && word + 4 <= wlim;
-            const uint4 x = *reinterpret_cast<const uint4*>(bits + (ok ? (uint64_t)row * wpk + word : 0));
-            v[i] = ok ? x : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto store_sel = [&](const uint4 (&v)[kPer]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < kPer; ++i) {
-            const uint32_t p = threadIdx.x + (uint32_t)i * 64 * NW;
-            if (p < (uint32_t)kPieces) *reinterpret_cast<uint4*>(&s_sel[(p / (2 * SG)) * kRow + 4 * (p % (2 * SG))]) = v[i];
-        }
-    };
-    // DB pieces of a whole block (clamped past the range; never folded).  A
-    // tile the record does not have is not loaded: zeros.
-    auto load_db = [&](uint64_t sb, uint4 (&B)[SG][NT]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl) {
-            const uint64_t S = sb + sl < s1 ? sb + sl : s1 - 1;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                B[sl][j] = make_uint4(0, 0, 0, 0);
-                if ((uint32_t)j < nt) B[sl][j] = fold_ld<NTDB>(&dbs[((S * ntiles + tile0 + j) * 32 + r) * 2 + h]);
-            }
-        }
-    };
-    fold_v16f acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.0f;
-    // One super-group: 4 K-blocks of 64 records x MT x NT MFMAs.
-    auto fold_sg = [&](int sl, const uint4 (&B)[NT]) __attribute__((always_inline)) {
-        uint4 A[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-            A[m] = *reinterpret_cast<const uint4*>(&s_sel[(32 * m + r) * kRow + 8 * sl + 4 * h]);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            fold_v8i bo[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bo[j] = fp4_db<SC>(u4w(B[j], t));
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const fold_v8i ao = fp4_sel<SC>(u4w(A[m], t));
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[m][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bo[j], acc[m][j], kFoldFp4, kFoldFp4,
-                                                                               0, kE8M0One, 0, kE8M0One);
-            }
-        }
-    };
-    uint4 sv[kPer];
-    uint4 BA[SG][NT], BB[SG][NT];
-    load_sel(s0, sv);
-    load_db(s0, BA);
-    // One staged block: its selection rows to LDS, the next block's loads
-    // issued, then its super-groups folded.
-    auto block = [&](uint64_t sb, const uint4 (&Bc)[SG][NT], uint4 (&Bn)[SG][NT]) __attribute__((always_inline)) {
-        lds_barrier();                                          // previous block's operand reads are done
-        store_sel(sv);
-        lds_barrier();
-        const uint64_t nb = sb + SG < s1 ? sb + SG : sb;        // next block (clamped)
-        load_sel(nb, sv);
-        load_db(nb, Bn);
-        const uint64_t n = s1 - sb;
-#pragma unroll
-        for (int sl = 0; sl < SG; ++sl)
-            if ((uint64_t)sl < n && nt != 0) fold_sg(sl, Bc[sl]);
-    };
-    uint64_t sb = s0;
-    for (; sb + SG < s1; sb += 2 * SG) {
-        block(sb, BA, BB);
-        block(sb + SG, BB, BA);
-    }
-    if (sb < s1) block(sb, BA, BB);
-    // Parities -> answer words: parts[x][key][8 CG y] (word = 8 * column of the launch + bit tile).
-    constexpr uint32_t pkeys = 32 * MT;
+#define FOLD_UNIT                                             \
+    const uint64_t col0 = (uint64_t)(cg0 + blockIdx.y) * CG; \
+    const uint32_t* const sel = bits;                        \
+    const uint64_t stride = wpk;                             \
+    const uint32_t nrows = nkeys;
+#define FOLD_RUN                                                          \
+    const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;               \
+    const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg; \
+    if (s0 >= s1) return; /* uniform over the workgroup */
+#define FOLD_DB_AT(S, j) &dbs[((S * ntiles + tile0 + j) * 32 + r) * 2 + h]
+    // Answer words: parts[x][key][8 CG y] (word = 8 * column of the launch + bit tile).
+#define FOLD_EMIT_BEGIN              \
+    constexpr uint32_t pkeys = 32 * MT; \
     const uint32_t pwords = 8u * CG * gridDim.y;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            uint32_t out = 0;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t p = ((uint32_t)acc[m][j][e]) & 1u;
-                const uint64_t b = __builtin_amdgcn_ballot_w64(p != 0);
-                const uint32_t row0 = (e & 3) + 8 * (e >> 2);
-                out = l == row0 ? (uint32_t)b : out;
-                out = l == row0 + 4 ? (uint32_t)(b >> 32) : out;
-            }
-            if (l < 32 && (uint32_t)j < nt)
-                parts[((uint64_t)blockIdx.x * pkeys + 32 * m + l) * pwords + (blockIdx.y * CG + cw) * 8 + w * NT + j] = out;
-        }
+#define FOLD_EMIT(m, j, out)          \
+    if (l < 32 && (uint32_t)j < nt) \
+        parts[((uint64_t)blockIdx.x * pkeys + 32 * m + l) * pwords + (blockIdx.y * CG + cw) * 8 + w * NT + j] = out;
+#include "fold_mfma_body.inc"
 }
 
 // The sliced layout (above) from a row-major DB of 32 C-byte records.
@@ -273,7 +174,8 @@ __global__ __launch_bounds__(256) void k_slice_db(const uint4* __restrict__ db, 
     }
 }
 
-// One key over the sliced DB: no matrix product needed.  Workgroup (x, y)
+// One key over the sliced DB: no matrix product needed (the loop is
+// fold_popcount_body.inc, shared with k_fold_grouped).  Workgroup (x, y)
 // folds super-group run x of column c0 + y; thread n of its 256 owns bit
 // position n of that column.  Per super-group it reads its 8 words
 // dbs[S][c][n][0..7] (the workgroup: 8 KiB contiguous) and XORs (selection
@@ -297,33 +199,14 @@ __global__ __launch_bounds__(256) void k_fold_sliced_direct(const uint32_t* __re
     const uint64_t col = c0 + blockIdx.y;
     const uint64_t s0 = (uint64_t)blockIdx.x * sg_per_block;
     const uint64_t s1 = s0 + sg_per_block < nsg ? s0 + sg_per_block : nsg;
-    uint32_t acc = 0;
-    auto fold = [&](uint64_t S, const uint4& a, const uint4& b) __attribute__((always_inline)) {
-        const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        if (8 * S + 8 <= wlim) {                               // uniform
-#pragma unroll
-            for (int g = 0; g < 8; ++g) acc = xam(acc, x[g], bits[8 * S + g]);
-        } else {                                               // the key row ends inside this super-group
-#pragma unroll
-            for (int g = 0; g < 8; ++g)
-                if (8 * S + g < wlim) acc = xam(acc, x[g], bits[8 * S + g]);
-        }
-    };
-    const uint64_t row = col * 256 + n;
-    auto at = [&](uint64_t S) { return &dbs[(S * nrows + row) * 2]; };
-    if (row < nrows) {
-        uint64_t S = s0;
-        for (; S + 1 < s1; S += 2) {
-            const uint4 a0 = at(S)[0], b0 = at(S)[1];
-            const uint4 a1 = at(S + 1)[0], b1 = at(S + 1)[1];
-            fold(S, a0, b0);
-            fold(S + 1, a1, b1);
-        }
-        if (S < s1) fold(S, at(S)[0], at(S)[1]);
-    }
-    const uint64_t m = __builtin_amdgcn_ballot_w64((__builtin_popcount(acc) & 1) != 0);
-    if (l < 2)
-        parts[(uint64_t)blockIdx.x * (8u * gridDim.y) + 8 * blockIdx.y + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
+    constexpr int KP = 1;
+#define FOLD_ONE_KEY
+#define FOLD_SEL(j, i) bits[i]
+#define FOLD_AT(S) &dbs[(S * nrows + row) * 2]
+#define FOLD_EMIT_BEGIN
+#define FOLD_EMIT(j, m) \
+    if (l < 2) parts[(uint64_t)blockIdx.x * (8u * gridDim.y) + 8 * blockIdx.y + 2 * w + l] = l ? (uint32_t)(m >> 32) : (uint32_t)m;
+#include "fold_popcount_body.inc"
 }
 
 uint64_t pir_sliced_bytes(uint64_t nrec, uint64_t rec_bytes) { return (nrec + 255) / 256 * 256 * rec_bytes; }
@@ -432,17 +315,9 @@ hipError_t launch_pir_fold_sliced(const uint32_t* bits, uint64_t words_per_key, 
         const uint32_t* b = bits + (uint64_t)k0 * words_per_key;
         const uint64_t zw = dpfh::fold_clear_words_any(nkeys, rec_bytes, k0);
         uint32_t* a = ans + (uint64_t)k0 * T;
-        hipError_t e;
-        static_assert(dpfh::kFoldTileCount == 7, "one case per tile shape");
-        switch (dpfh::fold_tile_index(nk, cg)) {
-            case 0: e = launch_mfma<0>(f, b, nk, a, zw); break;
-            case 1: e = launch_mfma<1>(f, b, nk, a, zw); break;
-            case 2: e = launch_mfma<2>(f, b, nk, a, zw); break;
-            case 3: e = launch_mfma<3>(f, b, nk, a, zw); break;
-            case 4: e = launch_mfma<4>(f, b, nk, a, zw); break;
-            case 5: e = launch_mfma<5>(f, b, nk, a, zw); break;
-            default: e = launch_mfma<6>(f, b, nk, a, zw); break;
-        }
+        const hipError_t e = dpfh::with_fold_tile(dpfh::fold_tile_index(nk, cg), [&](auto shape) {
+            return launch_mfma<decltype(shape)::value>(f, b, nk, a, zw);
+        });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
