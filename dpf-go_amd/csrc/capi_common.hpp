@@ -30,6 +30,7 @@
 #include "eval_bits_plan.hpp"
 #include "pir_group_plan.hpp"
 #include "pir_kernels.hpp"
+#include "pir_window_plan.hpp"
 #include "stage_plan.hpp"
 
 namespace dpfc {
@@ -263,6 +264,49 @@ inline GroupSparseWs group_sparse_ws(void* d_work, size_t nkeys, uint64_t nrec, 
     return w;
 }
 
+// d_work of the window forms (pir_window_plan.hpp): [sub-keys, nkeys * P of
+// the canonical length | tree workspace of nkeys * P keys at logN' = s | rows
+// [nkeys][row_bytes] | the fold's partials], each of the first three padded
+// to 256 B.  dpf_evalfull_window_dev uses the first two parts (its rows are
+// the caller's), the PIR composites all four.  On the subtree route there are
+// no sub-keys: the tree workspace is that of nkeys keys at logN below the
+// window's prefix, at the front.
+struct WindowWs {
+    dpfh::WindowPlan plan;
+    size_t nsub, sub_len;    // sub-keys (0 on the subtree route) and their length
+    uint8_t* sub;
+    void* tree;
+    uint8_t* rows;
+    uint32_t* parts;
+    size_t evalfull_total, total;
+};
+inline WindowWs window_ws(void* d_work, size_t nkeys, uint32_t logN, uint64_t first_block, uint64_t nblocks) {
+    WindowWs w;
+    w.plan = dpfh::window_plan(logN, first_block, nblocks);
+    const bool pieces = w.plan.route == dpfh::kWindowPieces;
+    w.nsub = pieces ? nkeys * (size_t)w.plan.npieces : 0;
+    w.sub_len = (size_t)dpfh::window_canonical_sub_key_len(w.plan);
+    const size_t sub = align256(w.nsub * w.sub_len);
+    const size_t tree = align256(pieces ? tree_ws_bytes(w.nsub, stop_of(w.plan.s), 0, w.nsub)
+                                        : tree_ws_bytes(nkeys, stop_of(logN), w.plan.prefix_bits, nkeys));
+    // (+16: the fold reads whole super-groups' words, 32 bytes, of a window of 16-byte blocks.)
+    const size_t rows = align256(nkeys * (size_t)w.plan.row_bytes + 16);
+    w.sub = at(d_work, 0);
+    w.tree = at(d_work, sub);
+    w.rows = at(d_work, sub + tree);
+    w.parts = (uint32_t*)at(d_work, sub + tree + rows);
+    w.evalfull_total = std::max<size_t>(16, sub + tree);
+    w.total = sub + tree + rows + dpfk::pir_fold_parts_bytes();
+    return w;
+}
+
+// The window EvalFull of the three window entries, arguments checked: the
+// sub-keys and one tree launch over all of them where a key's pieces land
+// side by side (row_stride == row_bytes), else a launch per key; on the
+// subtree route the one prefixed tree launch of the dense forms.
+hipError_t window_evalfull(const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, const WindowWs& w,
+                           uint8_t* d_rows, size_t row_stride, hipStream_t st);
+
 // ---- expanded keys in a caller's d_work (dpf_capi.hip) -----------------------
 // Every entry point that expands keys into a caller's d_work records what it
 // left there (the tree_ws layout), so a later dpf_evalfull_expanded_dev never
@@ -332,6 +376,36 @@ inline int check_subtree(size_t klen, uint32_t logN, uint32_t prefix_bits, uint6
     if (!dpfh::prefix_ok(prefix_bits, prefix, stop_of(logN))) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
     const uint64_t slice = logN - prefix_bits >= 64 ? ~0ull : (1ull << (logN - prefix_bits));
     if (nrec > slice) return fail(DPF_ERR_PARAM, "dpf: more DB records than the subtree's domain");
+    return DPF_OK;
+}
+
+// A window of leaf blocks of the keys' domain: the key, at least one block,
+// inside the domain.
+inline int check_window(size_t klen, uint32_t logN, uint64_t first_block, uint64_t nblocks) {
+    if (int rc = check_key(klen, logN)) return rc;
+    if (!dpfh::window_ok(logN, first_block, nblocks)) return fail(DPF_ERR_PARAM, "dpf: window outside the 2^logN domain");
+    return DPF_OK;
+}
+// Records [first_rec, first_rec + nrec) of the keys' domain behind a window.
+inline int check_window_records(size_t klen, uint32_t logN, uint64_t first_rec, uint64_t nrec) {
+    if (int rc = check_key(klen, logN)) return rc;
+    if (first_rec % 128 != 0) return fail(DPF_ERR_PARAM, "dpf: first_rec must be a multiple of 128");
+    if (!dpfh::window_records_ok(logN, first_rec, nrec)) return fail(DPF_ERR_PARAM, "dpf: records outside the 2^logN domain");
+    return DPF_OK;
+}
+// Consecutive prefixes [first_prefix, first_prefix + nprefix) at depth
+// prefix_bits of the keys' tree.
+inline int check_prefix_run(size_t klen, uint32_t logN, uint32_t prefix_bits, uint64_t first_prefix, uint64_t nprefix) {
+    if (int rc = check_key(klen, logN)) return rc;
+    if (prefix_bits > stop_of(logN)) return fail(DPF_ERR_PARAM, "dpf: prefix_bits > logN - 7");
+    const uint64_t all = 1ull << prefix_bits;   // (prefix_bits <= 56)
+    if (first_prefix > all || nprefix > all - first_prefix) return fail(DPF_ERR_PARAM, "dpf: subtree prefix out of range");
+    return DPF_OK;
+}
+// Rows a window EvalFull writes, row_stride bytes a key.
+inline int check_window_rows(size_t row_stride, uint64_t row_bytes) {
+    if (row_stride % 16 != 0 || row_stride < row_bytes)
+        return fail(DPF_ERR_PARAM, "dpf: row_stride must be a multiple of 16, at least the window form's row_bytes");
     return DPF_OK;
 }
 

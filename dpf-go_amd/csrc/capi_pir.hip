@@ -374,6 +374,56 @@ int dpf_pir_write_sliced_any_dev(int device, const uint8_t* d_keys, size_t klen,
                      rec_bytes, d_work, stream);
 }
 
+// ---- PIR over any record range: records [first_rec, first_rec + nrec) of the domain ----
+// The selection bits come from the window EvalFull (window_evalfull: sub-keys
+// and one tree launch over them, or the prefixed launch of the forms above
+// where the window is one subtree) into rows inside d_work; the fold and the
+// scatter read them at row_offset, stride row_bytes.
+size_t dpf_pir_window_workspace_size(size_t nkeys, uint32_t logN, uint64_t first_rec, uint64_t nrec, size_t rec_bytes) {
+    if (!rec_bytes_ok(RecRule::Mul4, rec_bytes) || !dpfh::window_records_ok(logN, first_rec, nrec)) return 0;
+    if (nrec == 0) return 16;
+    return window_ws(nullptr, nkeys, logN, first_rec / 128, dpfh::window_blocks_of(nrec)).total;
+}
+
+int dpf_pir_answer_window_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, uint64_t first_rec,
+                              const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans, void* d_work,
+                              void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_window_records(klen, logN, first_rec, nrec)) return rc;
+    if (int rc = check_answer_bufs(d_keys, nkeys, d_dbs, nrec, d_ans, d_work)) return rc;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (nkeys == 0) return DPF_OK;
+    if (nrec == 0) {
+        HIP_TRY(dpfk::launch_zero(d_ans, nkeys * rec_bytes, st));
+        return DPF_OK;
+    }
+    const WindowWs w = window_ws(d_work, nkeys, logN, first_rec / 128, dpfh::window_blocks_of(nrec));
+    HIP_TRY(window_evalfull(d_keys, klen, nkeys, logN, w, w.rows, w.plan.row_bytes, st));
+    HIP_TRY(fold_launcher(true)((const uint32_t*)(w.rows + w.plan.row_offset), w.plan.row_bytes / 4, d_dbs, nrec, rec_bytes,
+                                (uint32_t)nkeys, (uint32_t*)d_ans, w.parts, st));
+    return DPF_OK;
+}
+
+int dpf_pir_write_window_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, uint64_t first_rec,
+                             const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, void* d_work,
+                             void* stream) {
+    if (int rc = check_rec_bytes(RecRule::Mul4, rec_bytes)) return rc;
+    if (int rc = check_window_records(klen, logN, first_rec, nrec)) return rc;
+    if (!present(d_keys, d_msgs, d_dbs, d_work)) return null_buffer();
+    if (!aligned(16, d_msgs, d_dbs, d_work)) return misaligned_buffer();
+    if (nkeys == 0 || nrec == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    hipStream_t st = (hipStream_t)stream;
+    const WindowWs w = window_ws(d_work, nkeys, logN, first_rec / 128, dpfh::window_blocks_of(nrec));
+    HIP_TRY(window_evalfull(d_keys, klen, nkeys, logN, w, w.rows, w.plan.row_bytes, st));
+    HIP_TRY(scatter_launcher(true)((const uint32_t*)(w.rows + w.plan.row_offset), w.plan.row_bytes / 4, d_dbs, nrec, rec_bytes,
+                                   d_msgs, nkeys, st));
+    return DPF_OK;
+}
+
 // ---- PIR over a sparse key set: record j lives at domain point d_points[j] ----
 // The selection bits come from the Eval-bits launches at the records' points,
 // not from an EvalFull of a subtree; the fold and the scatter are the dense ones.

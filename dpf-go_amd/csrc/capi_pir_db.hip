@@ -32,6 +32,11 @@ struct PirDb {
     // lives at domain point points[j]): a range of whole super-groups and not
     // a subtree (pbits = 0), with its slice of the points beside it in HBM.
     bool sparse = false;
+    // Ranged (dpf_pir_db_create_ranged): dense, record j at domain point j, but
+    // sharded by the sparse kind's record ranges (pbits = 0); a shard answers
+    // and writes through the window forms with first_rec = ranges.lo(g).
+    bool ranged = false;
+    bool by_ranges() const { return sparse || ranged; }   // the range bookkeeping of update / read / export
     // Grouped (dpf_pir_db_create_grouped): ngroups
     // groups of gnrec records, nrec = ngroups * gnrec the caller's index space.
     // Shard s holds the whole groups [group_lo(s), group_hi(s)), gps of them,
@@ -220,8 +225,11 @@ int pir_db_create_grouped(const uint64_t* points, bool sparse, const uint8_t* db
 // rule: RecRule::Mul32 (dpf_pir_db_create, _wide) or Bytes1 (_any and _sparse:
 // every width from 1 byte, shards at w4 bytes per record).  points: the
 // sparse kind (any device count; each shard with its points beside it).
-int pir_db_create(RecRule rule, const uint64_t* points, bool sparse, const uint8_t* db, uint64_t nrec, size_t caller_bytes,
-                  uint32_t logN, int ngpus, void** handle) {
+// Ranged: the dense kind over the sparse kind's record ranges.
+enum class DbKind { Dense, Sparse, Ranged };
+int pir_db_create(RecRule rule, const uint64_t* points, DbKind kind, const uint8_t* db, uint64_t nrec,
+                  size_t caller_bytes, uint32_t logN, int ngpus, void** handle) {
+    const bool sparse = kind == DbKind::Sparse, ranged = kind == DbKind::Ranged;
     // What needs no device.
     if (!handle) return fail(DPF_ERR_PARAM, "dpf: null handle");
     *handle = nullptr;
@@ -238,7 +246,7 @@ int pir_db_create(RecRule rule, const uint64_t* points, bool sparse, const uint8
     if (have <= 0) return have;
     const int want = ngpus <= 0 ? have : ngpus;
     uint32_t pb = 0;
-    if (sparse) {
+    if (sparse || ranged) {
         if (want > have) return fail(DPF_ERR_PARAM, "dpf: ngpus must be <= opened devices");
     } else if (want > have || !dpfh::gpus_to_pb(want, stop_of(logN), &pb)) {
         return fail(DPF_ERR_PARAM, "dpf: ngpus must be a power of two <= opened devices and 2^(logN-7)");
@@ -254,8 +262,11 @@ int pir_db_create(RecRule rule, const uint64_t* points, bool sparse, const uint8
         return fail(DPF_ERR_PARAM, "dpf: row-major shards (DPF_PIR_FOLD=lds) take multiples of 32 bytes only");
     if (!h->sliced && sparse)
         return fail(DPF_ERR_PARAM, "dpf: sparse handles keep sliced shards only (DPF_PIR_FOLD=lds set)");
+    if (!h->sliced && ranged)
+        return fail(DPF_ERR_PARAM, "dpf: ranged handles keep sliced shards only (DPF_PIR_FOLD=lds set)");
     h->sparse = sparse;
-    h->ranges = sparse ? dpfh::sparse_shards(nrec, (size_t)want) : dpfh::dense_shards(nrec, logN, pb);
+    h->ranged = ranged;
+    h->ranges = sparse || ranged ? dpfh::sparse_shards(nrec, (size_t)want) : dpfh::dense_shards(nrec, logN, pb);
     // The uploads.
     for (int g = 0; g < want; ++g)
         if (int rc = upload_shard(h.get(), devs[(size_t)g], (size_t)g, db, points)) return rc;
@@ -278,6 +289,9 @@ int on_shard(PirDb* h, size_t s, const uint8_t* keys, size_t klen, size_t nkeys,
     HIP_TRY(d.work.ensure(h->grouped && h->sparse ? dpf_pir_grouped_sparse_workspace_size(1, nkeys, h->gnrec, h->logN, h->w4)
                           : h->grouped            ? dpf_pir_grouped_workspace_size(1, nkeys, h->logN, h->w4)
                           : h->sparse             ? dpf_pir_sparse_workspace_size(nkeys, h->shard_n[s], h->logN)
+                          : h->ranged
+                              ? dpf_pir_window_workspace_size(nkeys, h->logN, h->shard_n[s] ? h->ranges.lo(s) : 0,
+                                                              h->shard_n[s], h->w4)
                                                   : dpf_pir_workspace_size(nkeys, h->logN, h->pbits)));
     HIP_TRY(d.out.ensure(out_bytes));
     HIP_TRY(hipMemcpyAsync(d.keys.p, keys, nkeys * klen, hipMemcpyHostToDevice, d.st));
@@ -319,6 +333,11 @@ int shard_dev(PirDb* h, size_t s, Dev& d, size_t klen, size_t nkeys, bool write)
         const uint64_t* pts = (const uint64_t*)h->shard_pts[s];
         return write ? dpf_pir_write_sparse_dev(d.id, k, klen, nkeys, h->logN, pts, io, db, n, h->w4, d.work.p, d.st)
                      : dpf_pir_answer_sparse_dev(d.id, k, klen, nkeys, h->logN, pts, db, n, h->w4, io, d.work.p, d.st);
+    }
+    if (h->ranged) {
+        const uint64_t first = n ? h->ranges.lo(s) : 0;   // (a shard the split left empty starts at nrec)
+        return write ? dpf_pir_write_window_dev(d.id, k, klen, nkeys, h->logN, first, io, db, n, h->w4, d.work.p, d.st)
+                     : dpf_pir_answer_window_dev(d.id, k, klen, nkeys, h->logN, first, db, n, h->w4, io, d.work.p, d.st);
     }
     if (write)
         return (h->sliced ? dpf_pir_write_sliced_any_dev : dpf_pir_write_wide_dev)(
@@ -383,8 +402,9 @@ int pir_update_or_read(void* handle, const uint64_t* idx, size_t n, const uint8_
     if (!idx || (!recs && !out)) return fail(DPF_ERR_PARAM, "dpf: null buffer");
     dpfh::PirUpdatePlan plan;
     if (!(h->grouped  ? dpfh::plan_pir_update_grouped(idx, n, h->ngroups, h->gnrec, h->shard.size(), recs != nullptr, &plan)
-          : h->sparse ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->ranges.slice, h->shard.size(), recs != nullptr, &plan)
-                      : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
+          : h->by_ranges()
+              ? dpfh::plan_pir_update_ranges(idx, n, h->nrec, h->ranges.slice, h->shard.size(), recs != nullptr, &plan)
+              : dpfh::plan_pir_update(idx, n, h->nrec, h->logN, h->pbits, recs != nullptr, &plan)))
         return fail(DPF_ERR_PARAM, "dpf: record index outside the DB");
     const size_t chunk = std::max<size_t>(1, kPirUploadChunk / h->w4);
     std::vector<uint8_t> host;
@@ -404,8 +424,8 @@ std::atomic<size_t> g_export_chunk{0};
 int plan_range(PirDb* h, uint64_t first, uint64_t n, std::vector<dpfh::ExportPiece>* pieces) {
     const size_t lim = g_export_chunk.load(std::memory_order_relaxed);
     const dpfh::ExportKind kind = h->grouped  ? dpfh::ExportKind::Grouped
-                                  : h->sparse ? dpfh::ExportKind::Sparse
-                                              : dpfh::ExportKind::Dense;
+                                  : h->by_ranges() ? dpfh::ExportKind::Sparse
+                                                   : dpfh::ExportKind::Dense;
     if (!dpfh::plan_export(kind, first, n, (lim ? lim : kPirUploadChunk) / h->w4, h->ranges, h->shard.size(), h->ngroups,
                            h->gnrec, pieces))
         return fail(DPF_ERR_PARAM, "dpf: record range outside the DB");
@@ -472,18 +492,21 @@ int pir_export_or_xor(void* handle, uint64_t first, uint64_t n, uint8_t* out, co
 extern "C" {
 
 int dpf_pir_db_create(const uint8_t* db, uint64_t nrec, uint32_t logN, int ngpus, void** handle) {
-    return pir_db_create(RecRule::Mul32, nullptr, false, db, nrec, 32, logN, ngpus, handle);
+    return pir_db_create(RecRule::Mul32, nullptr, DbKind::Dense, db, nrec, 32, logN, ngpus, handle);
 }
 int dpf_pir_db_create_wide(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus,
                            void** handle) {
-    return pir_db_create(RecRule::Mul32, nullptr, false, db, nrec, rec_bytes, logN, ngpus, handle);
+    return pir_db_create(RecRule::Mul32, nullptr, DbKind::Dense, db, nrec, rec_bytes, logN, ngpus, handle);
 }
 int dpf_pir_db_create_any(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle) {
-    return pir_db_create(RecRule::Bytes1, nullptr, false, db, nrec, rec_bytes, logN, ngpus, handle);
+    return pir_db_create(RecRule::Bytes1, nullptr, DbKind::Dense, db, nrec, rec_bytes, logN, ngpus, handle);
 }
 int dpf_pir_db_create_sparse(const uint64_t* points, const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN,
                              int ngpus, void** handle) {
-    return pir_db_create(RecRule::Bytes1, points, true, db, nrec, rec_bytes, logN, ngpus, handle);
+    return pir_db_create(RecRule::Bytes1, points, DbKind::Sparse, db, nrec, rec_bytes, logN, ngpus, handle);
+}
+int dpf_pir_db_create_ranged(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle) {
+    return pir_db_create(RecRule::Bytes1, nullptr, DbKind::Ranged, db, nrec, rec_bytes, logN, ngpus, handle);
 }
 int dpf_pir_db_create_grouped(const uint8_t* db, uint64_t ngroups, uint64_t nrec, size_t rec_bytes, uint32_t logN,
                               int ngpus, void** handle) {

@@ -215,6 +215,27 @@ hipError_t dpfc::tree_from_keys(const uint8_t* d_keys, size_t klen, size_t nk, u
     return e;
 }
 
+hipError_t dpfc::window_evalfull(const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, const WindowWs& w,
+                                 uint8_t* d_rows, size_t row_stride, hipStream_t st) {
+    const dpfh::WindowPlan& p = w.plan;
+    const bool bs = want_bs();
+    if (p.route == dpfh::kWindowSubtree)
+        return tree_from_keys(d_keys, klen, nkeys, stop_of(logN), p.prefix_bits, p.first_prefix, d_rows, row_stride, w.tree, st,
+                              bs);
+    forget_expanded(w.sub);   // d_work itself: the sub-keys overwrite what a dense call expanded there
+    hipError_t e = dpfk::launch_subkeys(d_keys, klen, nkeys, p.prefix_bits, p.first_prefix, p.npieces, w.sub, w.sub_len, st);
+    if (e != hipSuccess) return e;
+    const uint32_t stop = stop_of(p.s);
+    if (row_stride == p.row_bytes)
+        e = tree_from_keys(w.sub, w.sub_len, w.nsub, stop, 0, 0, d_rows, p.piece_bytes, w.tree, st, bs);
+    else
+        for (size_t k = 0; k < nkeys && e == hipSuccess; ++k)
+            e = tree_from_keys(w.sub + k * p.npieces * w.sub_len, w.sub_len, p.npieces, stop, 0, 0, d_rows + k * row_stride,
+                               p.piece_bytes, w.tree, st, bs);
+    forget_expanded(w.tree);   // the sub-keys' records are no caller's: nothing for dpf_evalfull_expanded_dev
+    return e;
+}
+
 hipError_t dpfc::eval_bits_launch(const uint8_t* d_keys, size_t klen, size_t nkeys, size_t keys_per_list,
                                   const uint64_t* d_xs, size_t npts, uint32_t logN, uint8_t* d_bits, size_t bits_stride,
                                   void* d_work, size_t work_bytes, hipStream_t st) {
@@ -603,6 +624,57 @@ int dpf_evalfull_subtree_dev(int device, const uint8_t* d_keys, size_t klen, siz
 int dpf_evalfull_batch_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN,
                            uint8_t* d_out, void* d_work, void* stream) {
     return dpf_evalfull_subtree_dev(device, d_keys, klen, nkeys, logN, 0, 0, d_out, d_work, stream);
+}
+
+// ---- windows of the domain: re-rooted sub-keys (pir_window_plan.hpp) ----
+int dpf_window_form_for(uint32_t logN, uint64_t first_block, uint64_t nblocks, size_t klen, dpf_window_form* form) {
+    if (form == nullptr) return fail(DPF_ERR_PARAM, "dpf: null form pointer");
+    if (int rc = check_window(klen, logN, first_block, nblocks)) return rc;
+    const dpfh::WindowPlan p = dpfh::window_plan(logN, first_block, nblocks);
+    memset(form, 0, sizeof *form);
+    form->route = p.route;
+    form->prefix_bits = p.prefix_bits;
+    form->first_prefix = p.first_prefix;
+    form->npieces = p.npieces;
+    form->piece_bytes = p.piece_bytes;
+    form->row_bytes = p.row_bytes;
+    form->row_offset = p.row_offset;
+    form->sub_key_len = p.route == dpfh::kWindowPieces ? dpfh::window_sub_key_len(klen, p.prefix_bits) : klen;
+    return DPF_OK;
+}
+
+int dpf_subkeys_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, uint32_t prefix_bits,
+                    uint64_t first_prefix, uint64_t nprefix, uint8_t* d_sub, void* stream) {
+    if (int rc = check_prefix_run(klen, logN, prefix_bits, first_prefix, nprefix)) return rc;
+    // A key's last 16 bytes are its final CW: they lie behind the records of the levels walked.
+    if (klen < 17 + 18 * (size_t)prefix_bits + 16)
+        return fail(DPF_ERR_KEYLEN, "dpf: key shorter than 33+18*prefix_bits bytes");
+    if (nkeys == 0 || nprefix == 0) return DPF_OK;
+    if (!present(d_keys, d_sub)) return null_buffer();
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(dpfk::launch_subkeys(d_keys, klen, nkeys, prefix_bits, first_prefix, nprefix, d_sub,
+                                 dpfh::window_sub_key_len(klen, prefix_bits), (hipStream_t)stream));
+    return DPF_OK;
+}
+
+size_t dpf_evalfull_window_workspace_size(size_t nkeys, uint32_t logN, uint64_t first_block, uint64_t nblocks) {
+    if (!dpfh::window_ok(logN, first_block, nblocks)) return 0;
+    return window_ws(nullptr, nkeys, logN, first_block, nblocks).evalfull_total;
+}
+
+int dpf_evalfull_window_dev(int device, const uint8_t* d_keys, size_t klen, size_t nkeys, uint32_t logN, uint64_t first_block,
+                            uint64_t nblocks, uint8_t* d_rows, size_t row_stride, void* d_work, void* stream) {
+    if (int rc = check_window(klen, logN, first_block, nblocks)) return rc;
+    const WindowWs w = window_ws(d_work, nkeys, logN, first_block, nblocks);
+    if (int rc = check_window_rows(row_stride, w.plan.row_bytes)) return rc;
+    if (nkeys > 0 && !present(d_keys, d_rows, d_work)) return null_buffer();
+    if (!aligned(16, d_rows, d_work)) return misaligned_buffer();
+    if (nkeys == 0) return DPF_OK;
+    DeviceGuard g(device);
+    CuScope cus(stream);
+    HIP_TRY(window_evalfull(d_keys, klen, nkeys, logN, w, d_rows, row_stride, (hipStream_t)stream));
+    return DPF_OK;
 }
 
 size_t dpf_eval_workspace_size(size_t nkeys, size_t ppk, uint32_t logN) { return eval_ws_bytes(nkeys, ppk, logN); }

@@ -53,6 +53,15 @@ bool evalfull_raw_ok(uint64_t nkeys, uint32_t stop, uint32_t prefix_bits);
 hipError_t launch_evalfull_raw(const uint8_t* keys, uint64_t klen, uint64_t nkeys, uint32_t stop, uint32_t prefix_bits,
                                uint64_t prefix, uint8_t* out, uint64_t out_stride, hipStream_t st);
 
+// Re-rooted keys (k_subkeys, subkeys.hip): key k walked prefix_bits levels
+// along first_prefix + p, as a key of the subtree's domain, sub_len bytes at
+// sub + (k * nprefix + p) * sub_len, for p < nprefix.  sub_len = klen - 18 *
+// prefix_bits copies the key's tail unchanged (oracle.reroot_key); the
+// canonical 33 + 18 * (stop - prefix_bits) takes the records below the node
+// and the key's last 16 bytes.  Any alignment of keys and sub.
+hipError_t launch_subkeys(const uint8_t* keys, uint64_t klen, uint64_t nkeys, uint32_t prefix_bits, uint64_t first_prefix,
+                          uint64_t nprefix, uint8_t* sub, uint64_t sub_len, hipStream_t st);
+
 // The 2^(depth - prefix_bits) nodes at level `depth` below prefix node
 // (prefix_bits, prefix) of every key: seeds (16 B) at seeds + (key * stride
 // + j) * 16 and t bytes at ts + key * stride + j.

@@ -9,6 +9,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "pir_window_plan.hpp"
+
 namespace dpfh {
 
 constexpr size_t kPlanRadixMin = 4096;   // entries from which the planner sorts by radix
@@ -38,10 +40,11 @@ struct ShardRanges {
 inline ShardRanges dense_shards(uint64_t nrec, uint32_t logN, uint32_t pbits) {
     return ShardRanges{nrec, 1ull << (logN - pbits)};
 }
-// Sparse: an even split in whole super-groups of 256 records, so that every
-// shard's sliced layout starts on one (plan_pir_update_ranges with cap = slice).
+// Sparse, and the ranged dense kind: the balanced split in whole super-groups
+// of 256 records (pir_window_plan.hpp balanced_slice; plan_pir_update_ranges
+// with cap = slice).
 inline ShardRanges sparse_shards(uint64_t nrec, size_t nshards) {
-    return ShardRanges{nrec, ((nrec + 255) / 256 + (uint64_t)nshards - 1) / (uint64_t)nshards * 256};
+    return ShardRanges{nrec, balanced_slice(nrec, (uint64_t)nshards)};
 }
 
 // The planner behind both shardings below: split(v, &shard, &local) places

@@ -80,6 +80,12 @@ class FoldGroupedFormC(ctypes.Structure):
                 ("sg_per_run", _u64), ("units", _u64), ("passes", _u64), ("launches", _u64), ("max_blocks", _u64)]
 
 
+class WindowFormC(ctypes.Structure):
+    """dpf_window_form (include/dpf_hip.h)."""
+    _fields_ = [("route", _u32), ("prefix_bits", _u32), ("first_prefix", _u64), ("npieces", _u64), ("piece_bytes", _u64),
+                ("row_bytes", _u64), ("row_offset", _u64), ("sub_key_len", _u64)]
+
+
 # name -> (restype, argtypes); must cover every function in include/dpf_hip.h
 SIGNATURES = {
     "dpf_tree_form_for": (_int, [_sz, _u32, _u32, _u32, _int, ctypes.POINTER(TreeFormC)]),
@@ -114,6 +120,14 @@ SIGNATURES = {
     "dpf_pir_answer_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _u64, _sz, _vp, _vp, _vp]),
     "dpf_pir_write_sparse_dev": (_int, [_int, _vp, _sz, _sz, _u32, _vp, _vp, _vp, _u64, _sz, _vp, _vp]),
     "dpf_pir_db_create_sparse": (_int, [_u64p, _u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
+    "dpf_window_form_for": (_int, [_u32, _u64, _u64, _sz, ctypes.POINTER(WindowFormC)]),
+    "dpf_subkeys_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u32, _u64, _u64, _vp, _vp]),
+    "dpf_evalfull_window_workspace_size": (_sz, [_sz, _u32, _u64, _u64]),
+    "dpf_evalfull_window_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u64, _u64, _vp, _sz, _vp, _vp]),
+    "dpf_pir_window_workspace_size": (_sz, [_sz, _u32, _u64, _u64, _sz]),
+    "dpf_pir_answer_window_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u64, _vp, _u64, _sz, _vp, _vp, _vp]),
+    "dpf_pir_write_window_dev": (_int, [_int, _vp, _sz, _sz, _u32, _u64, _vp, _vp, _u64, _sz, _vp, _vp]),
+    "dpf_pir_db_create_ranged": (_int, [_u8p, _u64, _sz, _u32, _int, ctypes.POINTER(_vp)]),
     "dpf_pir_group_stride": (_u64, [_u64]),
     "dpf_pir_db_grouped_size": (_sz, [_u64, _u64, _sz]),
     "dpf_pir_db_slice_grouped_dev": (_int, [_int, _vp, _u64, _u64, _sz, _vp, _vp]),
@@ -819,6 +833,65 @@ def pir_write_sliced_any_dev(d_keys, key_len_: int, nkeys: int, logN: int, d_msg
                                               _stream_handle(stream)))
 
 
+# ---- windows of the domain: sub-keys, window EvalFull, PIR over any record range ----
+WINDOW_SUBTREE, WINDOW_PIECES = 0, 1
+WindowForm = collections.namedtuple(
+    "WindowForm", "route prefix_bits first_prefix npieces piece_bytes row_bytes row_offset sub_key_len")
+
+
+def window_form_for(logN: int, first_block: int, nblocks: int, key_len_: Optional[int] = None) -> "WindowForm":
+    """How the window forms evaluate leaf blocks [first_block, first_block +
+    nblocks) of a 2^logN domain (dpf_window_form_for): one aligned subtree
+    (WINDOW_SUBTREE) or npieces re-rooted sub-keys per key (WINDOW_PIECES),
+    the window starting at byte row_offset of a row.  Needs no device."""
+    c = WindowFormC()
+    _check(lib().dpf_window_form_for(logN, first_block, nblocks, key_len(logN) if key_len_ is None else key_len_,
+                                     ctypes.byref(c)))
+    return WindowForm(*[int(getattr(c, f)) for f in WindowForm._fields])
+
+
+def subkeys_dev(d_keys, key_len_: int, nkeys: int, logN: int, prefix_bits: int, first_prefix: int, nprefix: int, d_sub,
+                device: int = 0, stream=None) -> None:
+    """The device form of oracle.reroot_key: d_sub[k * nprefix + p] := key k as
+    the key of subtree (prefix_bits, first_prefix + p), key_len_ - 18 *
+    prefix_bits bytes each."""
+    _check(lib().dpf_subkeys_dev(device, _ptr(d_keys), key_len_, nkeys, logN, prefix_bits, first_prefix, nprefix,
+                                 _ptr(d_sub), _stream_handle(stream)))
+
+
+def evalfull_window_workspace_size(nkeys: int, logN: int, first_block: int, nblocks: int) -> int:
+    return int(lib().dpf_evalfull_window_workspace_size(nkeys, logN, first_block, nblocks))
+
+
+def evalfull_window_dev(d_keys, key_len_: int, nkeys: int, logN: int, first_block: int, nblocks: int, d_rows,
+                        row_stride: int, d_work, device: int = 0, stream=None) -> None:
+    """EvalFull of every key over the window's pieces: row k (window_form_for:
+    row_bytes, the window's 16 * nblocks bytes from row_offset) at d_rows + k *
+    row_stride."""
+    _check(lib().dpf_evalfull_window_dev(device, _ptr(d_keys), key_len_, nkeys, logN, first_block, nblocks, _ptr(d_rows),
+                                         row_stride, _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_window_workspace_size(nkeys: int, logN: int, first_rec: int, nrec: int, rec_bytes: int) -> int:
+    return int(lib().dpf_pir_window_workspace_size(nkeys, logN, first_rec, nrec, rec_bytes))
+
+
+def pir_answer_window_dev(d_keys, key_len_: int, nkeys: int, logN: int, first_rec: int, d_dbs, nrec: int, rec_bytes: int,
+                          d_ans, d_work, device: int = 0, stream=None) -> None:
+    """Server answers (nkeys x rec_bytes) over records [first_rec, first_rec +
+    nrec) of the domain (first_rec a multiple of 128), d_dbs their any-width
+    sliced layout: the window EvalFull, then the sliced fold."""
+    _check(lib().dpf_pir_answer_window_dev(device, _ptr(d_keys), key_len_, nkeys, logN, first_rec, _ptr(d_dbs), nrec,
+                                           rec_bytes, _ptr(d_ans), _ptr(d_work), _stream_handle(stream)))
+
+
+def pir_write_window_dev(d_keys, key_len_: int, nkeys: int, logN: int, first_rec: int, d_msgs, d_dbs, nrec: int,
+                         rec_bytes: int, d_work, device: int = 0, stream=None) -> None:
+    """The dual: record first_rec + j ^= XOR of the messages d_msgs[k] of the keys whose EvalFull has that bit set."""
+    _check(lib().dpf_pir_write_window_dev(device, _ptr(d_keys), key_len_, nkeys, logN, first_rec, _ptr(d_msgs),
+                                          _ptr(d_dbs), nrec, rec_bytes, _ptr(d_work), _stream_handle(stream)))
+
+
 # ---- PIR over a sparse key set: record j lives at domain point d_points[j] ----
 def pir_sparse_workspace_size(nkeys: int, nrec: int, logN: int) -> int:
     return int(lib().dpf_pir_sparse_workspace_size(nkeys, nrec, logN))
@@ -1002,6 +1075,13 @@ class PirDB:
     update()/read() take a record's position in the list.  The points are
     fixed at creation.
 
+    With `ranged=True` the handle is the ranged dense kind
+    (dpf_pir_db_create_ranged): record j still lives at domain point j, but
+    the shards are balanced record ranges (shard.record_range) over any number
+    of GPUs, each evaluated as a window of the domain (pir_answer_window_dev),
+    so a table that is not a power of two costs what its records cost and no
+    GPU is left empty.  Every method behaves as on the dense kind.
+
     With `groups=G` the handle is the grouped kind (dpf_pir_db_create_grouped):
     db is [G * nrec, rec] or [G, nrec, rec], G DBs of one shape, each with its
     own 2^logN domain and its own keys.  answer() takes keys [G * kpg, key_len]
@@ -1020,15 +1100,20 @@ class PirDB:
     take rows in group order, write() is refused, update() / read() / export()
     / xor_records() take idx = g * nrec + i, and clear() keeps the points."""
 
-    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None, groups=None):
+    def __init__(self, db: np.ndarray, logN: int, ngpus: int = 1, rec_bytes: int = 32, points=None, groups=None,
+                 ranged: bool = False):
         d = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
         if rec_bytes <= 0 or d.size % rec_bytes:
             raise ValueError("DB size must be a multiple of %d bytes" % rec_bytes)
+        if ranged and (points is not None or groups is not None):
+            raise ValueError("ranged=True is a kind of its own: no points, no groups")
         self.logN = logN
         self.rec_bytes = rec_bytes
         nrec = d.size // rec_bytes
         h = _vp()
-        if groups is not None:
+        if ranged:
+            _check(lib().dpf_pir_db_create_ranged(_buf(d), nrec, rec_bytes, logN, ngpus, ctypes.byref(h)))
+        elif groups is not None:
             if groups < 0 or (nrec % groups if groups else nrec):
                 raise ValueError("the DB must hold the same number of records for each of %d groups" % groups)
             per = nrec // groups if groups else 0

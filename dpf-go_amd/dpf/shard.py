@@ -9,6 +9,9 @@
               32 B per query; the partials are all-gathered (RCCL over xGMI,
               gloo on CPU) and XOR-combined on the host, because RCCL has no
               XOR reduction (configs[4]).
+  ranges    : the same over any world size: each rank holds a balanced record
+              range (record_range) and answers it as a window of the domain
+              (dpf.pir_answer_window_dev).
 """
 from __future__ import annotations
 
@@ -35,6 +38,18 @@ def db_slice(nrec_total: int, logN: int, world: int, rank: int) -> Tuple[int, in
     size = 1 << (logN - pb)
     lo = min(nrec_total, p * size)
     return lo, min(nrec_total, lo + size)
+
+
+def record_range(nrec_total: int, world: int, rank: int) -> Tuple[int, int]:
+    """Record range [lo, hi) of rank's shard under the balanced split of the
+    ranged and sparse PIR handles: ceil(ceil(nrec/256) / world) * 256 records
+    a rank, any world size.  lo is a multiple of 256, so a rank answers with
+    pir_answer_window_dev(first_rec=lo, nrec=hi - lo)."""
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank must be in [0, world)")
+    per = -(-(-(-nrec_total // 256)) // world) * 256
+    lo = min(nrec_total, rank * per)
+    return lo, min(nrec_total, lo + per)
 
 
 def xor_fold(parts: np.ndarray) -> np.ndarray:

@@ -629,6 +629,89 @@ int dpf_pir_db_read(void* handle, const uint64_t* idx, size_t n, uint8_t* out);
 int dpf_pir_db_write(void* handle, const uint8_t* keys, size_t key_len, size_t nkeys, const uint8_t* msgs);
 void dpf_pir_db_free(void* handle);
 
+/* ---- windows of the domain: sub-keys, window EvalFull, PIR over any range --
+ * A node (s, t) of the GGM tree with the remaining correction words is a DPF
+ * key of the smaller domain.  dpf_subkeys_dev is that re-rooting on the
+ * device: key k walked prefix_bits levels (<= logN - 7) along first_prefix + p
+ * becomes the key of subtree (prefix_bits, first_prefix + p), key_len - 18 *
+ * prefix_bits bytes (seed, t, then key bytes [17 + 18 * prefix_bits, key_len)
+ * unchanged) at d_sub[k * nprefix + p], for p < nprefix, first_prefix + nprefix
+ * <= 2^prefix_bits.  Its EvalFull at logN - prefix_bits is that subtree's slice
+ * of the deep key's EvalFull, byte for byte, for malformed keys too; every
+ * entry point that takes keys takes it.  key_len >= 33 + 18 * prefix_bits, no
+ * alignment of d_keys or d_sub.  prefix_bits = 0 copies the keys.
+ *
+ * A window is points [128 * first_block, 128 * (first_block + nblocks)) of the
+ * 2^logN domain (logN <= 63, nblocks >= 1, inside the domain, else
+ * DPF_ERR_PARAM).  dpf_window_form_for says, without a device, how the window
+ * forms evaluate it: DPF_WINDOW_SUBTREE where an aligned subtree of at most
+ * twice the window's points holds it (the window itself, where it is one; any
+ * window at logN < 7) -- the prefixed tree launch of dpf_evalfull_subtree_dev,
+ * one piece, the window at row_offset of the subtree's bytes -- else
+ * DPF_WINDOW_PIECES: npieces <= 33 consecutive aligned pieces of 2^s points, s
+ * = max(floor(log2(128 * nblocks)) - 4, 7), each the whole domain of one
+ * sub-key, so that at most two pieces' worth of points, under 1/8 of the
+ * window, is evaluated outside it.  (Measured on one MI355X, DESIGN.md 4.4: up
+ * to twice the points the one subtree is as fast or faster than the pieces.)
+ * dpf_evalfull_window_dev writes row k, the pieces of key k side by side
+ * (row_bytes = npieces * piece_bytes), at d_rows + k * row_stride; the
+ * window's 16 * nblocks bytes begin at byte row_offset of a row.  row_stride:
+ * a multiple of 16, at least row_bytes; with row_stride == row_bytes all
+ * nkeys * npieces sub-keys go through one tree launch, a larger stride takes
+ * one launch per key.  d_rows and d_work 16-byte aligned; d_work holds
+ * dpf_evalfull_window_workspace_size bytes (0 for a refused window).
+ *
+ * The PIR forms: d_dbs is the any-width sliced layout (rec_bytes a positive
+ * multiple of 4 up to DPF_PIR_MAX_REC_BYTES) of records [first_rec, first_rec
+ * + nrec) of the domain, first_rec a multiple of 128, first_rec + nrec <=
+ * 2^logN.  The answer for key k is the XOR of the records first_rec + j whose
+ * bit of EvalFull(key_k) is set (d_ans [nkeys][rec_bytes], overwritten; zeros
+ * for nrec == 0); the write is the dual.  Each is the window EvalFull of blocks
+ * [first_rec / 128, ... + ceil(nrec / 128)) into rows inside d_work, then
+ * dpf_xor_fold_sliced_any_dev / dpf_xor_scatter_sliced_any_dev from row_offset
+ * at stride row_bytes; DPF_PIR_FUSED has no part in either.  d_work holds
+ * dpf_pir_window_workspace_size bytes (0 for refused arguments).  Checked
+ * before any device call, in this order: rec_bytes, the key length
+ * (DPF_ERR_KEYLEN), first_rec, the range, then null and misaligned buffers as
+ * for the dense forms above.  All asynchronous on `stream`, with no
+ * allocation, memset or synchronisation: the stream-capture contract of the
+ * _dev calls above holds. */
+#define DPF_WINDOW_SUBTREE 0
+#define DPF_WINDOW_PIECES 1
+typedef struct dpf_window_form {
+    uint32_t route;         /* DPF_WINDOW_SUBTREE / DPF_WINDOW_PIECES */
+    uint32_t prefix_bits;   /* levels from the root to a piece's root */
+    uint64_t first_prefix;  /* the first piece among the 2^prefix_bits */
+    uint64_t npieces;
+    uint64_t piece_bytes;   /* EvalFull bytes of a piece */
+    uint64_t row_bytes;     /* npieces * piece_bytes */
+    uint64_t row_offset;    /* byte of a row at which the window starts, a multiple of 16 */
+    uint64_t sub_key_len;   /* key_len - 18 * prefix_bits (key_len on the subtree route) */
+} dpf_window_form;
+int dpf_window_form_for(uint32_t logN, uint64_t first_block, uint64_t nblocks, size_t key_len, dpf_window_form* form);
+int dpf_subkeys_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN, uint32_t prefix_bits,
+                    uint64_t first_prefix, uint64_t nprefix, uint8_t* d_sub, void* stream);
+size_t dpf_evalfull_window_workspace_size(size_t nkeys, uint32_t logN, uint64_t first_block, uint64_t nblocks);
+int dpf_evalfull_window_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                            uint64_t first_block, uint64_t nblocks, uint8_t* d_rows, size_t row_stride, void* d_work,
+                            void* stream);
+size_t dpf_pir_window_workspace_size(size_t nkeys, uint32_t logN, uint64_t first_rec, uint64_t nrec, size_t rec_bytes);
+int dpf_pir_answer_window_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                              uint64_t first_rec, const uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes, uint8_t* d_ans,
+                              void* d_work, void* stream);
+int dpf_pir_write_window_dev(int device, const uint8_t* d_keys, size_t key_len, size_t nkeys, uint32_t logN,
+                             uint64_t first_rec, const uint8_t* d_msgs, uint8_t* d_dbs, uint64_t nrec, size_t rec_bytes,
+                             void* d_work, void* stream);
+/* A resident DB of the ranged dense kind: record j lives at domain point j, as
+ * for dpf_pir_db_create_any, but the shards are balanced record ranges, not
+ * subtrees: ngpus is any count up to the opened devices (<= 0: all of them),
+ * shard g holds the ceil(ceil(nrec/256) / ngpus) * 256 records starting at g
+ * times that many (the sparse kind's split) and answers and writes through the
+ * window forms with that first_rec.  Every other handle call keeps its
+ * contract.  With env DPF_PIR_FOLD=lds (row-major shards) creation is
+ * DPF_ERR_PARAM. */
+int dpf_pir_db_create_ranged(const uint8_t* db, uint64_t nrec, size_t rec_bytes, uint32_t logN, int ngpus, void** handle);
+
 /* ---- PIR over a sparse key set (keyword PIR) ----------------------------
  * Record j of the DB lives at domain point d_points[j], any point of the
  * 2^logN domain, instead of at position j of a subtree: the client hashes its
